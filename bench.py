@@ -2,12 +2,16 @@
 """bench.py -- throughput of the auto_avsr training hot path (E2E forward + backward, video modality,
 12-layer Conformer / 6-layer decoder, --max-frames 1600 length-bucketed synthetic batches) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
-(one rank per GPU, RCCL).  Rank 0 prints ONE JSON line (contract in the task description): whole-job real
-(un-padded) video frames per second, plus `roofline` (dominant kernel family, MFMA bound) and `cpu_baseline`
-(the oracle timed on the host cores, N=1 only).
+(one rank per GPU, RCCL).  Rank 0 prints ONE JSON line: whole-job real (un-padded) video frames per second.
+
+A plain run does only what that headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+`--full` adds everything else the benchmark measures or checks, each in runs of its own AFTER the timed steps (N = 1):
+`roofline` (dominant kernel family, MFMA bound; + the HBM-bound family), `parity` (error against the reference goldens),
+`bf16` / `hpf` (the same workload timed in another numerical mode) and `cpu_baseline` (the oracle timed on the host cores);
+N > 1: `config.bucket_overlap` (one more eager step with an event pair around every gradient bucket).
 """
 import argparse
 import json
@@ -15,6 +19,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()  # (before `import torch`: the set-up figure printed to stderr counts the imports)
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -31,8 +36,12 @@ def parse():
     ap.add_argument("--babble", action="store_true",
                     help="audio only: configs[3] as specified -- every timed step starts from RAW waveforms and runs the reference's "
                          "AudioTransform('train') (time mask + babble noise at SNR 0 dB + layer norm) + padding collation on the device")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything besides the headline figure: roofline legs, parity "
+                         "blocks against the reference goldens, the bf16 leg (--hpf-leg: the hpf leg too), the CPU baseline; N > 1: the "
+                         "per-bucket overlap timing.  Off by default: a plain run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the `cpu_baseline` object")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the `roofline*` objects")
     ap.add_argument("--deterministic", action="store_true", help="time the bit-reproducible variant of the step (functional.set_deterministic)")
     ap.add_argument("--precise", action="store_true", help="parity mode (split-bf16 contractions) instead of bf16")
     ap.add_argument("--mode", choices=["bf16", "precise", "hpf", "mixed"], default=None,
@@ -42,10 +51,11 @@ def parse():
                          "bf16: bf16 operands everywhere (fastest, logits 7e-3 off the fp32 reference); hpf: every forward "
                          "contraction on split planes; precise: split planes forward and backward")
     ap.add_argument("--no-precise-leg", "--no-bf16-leg", dest="no_second_leg", action="store_true",
-                    help="skip the extra `bf16` object of the JSON line (throughput + parity of the plain bf16 mode on the same "
-                         "workload, N = 1 video)")
+                    help="--full without the extra `bf16` object of the JSON line (throughput + parity of the plain bf16 mode on the "
+                         "same workload, N = 1 video)")
     ap.add_argument("--hpf-leg", action="store_true",
-                    help="also time the hpf mode (every forward contraction on split planes) -> object `hpf` of the JSON line")
+                    help="--full only: also time the hpf mode (every forward contraction on split planes) -> object `hpf` of the "
+                         "JSON line")
     ap.add_argument("--shapes", type=int, default=8,
                     help="distinct length-bucketed batch shapes cycled through (spread over the bucket list; the longest "
                          "bucket, T = 400, is always one of them)")
@@ -55,7 +65,7 @@ def parse():
     ap.add_argument("--fixed", choices=["A", "B"], default=None,
                     help="time ONE fixed batch instead of the bucketed workload: the survey's batch A (4 x 400 frames, 64 "
                          "labels) or batch B (16 x 100, 16 labels), SURVEY.md section 8d")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity block (reference goldens at batch A)")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity blocks (reference goldens at batches A and B)")
     ap.add_argument("--ddp", choices=["auto", "torch", "buckets", "buckets-graph", "buckets-graph1"], default="auto",
                     help="N > 1 gradient exchange.  buckets-graph: this build's bucketed RCCL all-reduce (auto_avsr_amd/ddp.py) with every "
                          "collective of the step issued through RCCL's C API as a plain stream operation (auto_avsr_amd/comm.py) on two "
@@ -73,6 +83,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.hpf_leg and not args.full:
+        ap.error("--hpf-leg is one of the extra legs: it needs --full")
     return args
 
 
@@ -556,7 +568,11 @@ def main():
             dist.barrier()
         return time.perf_counter() - t0, last
 
+    t_setup = time.perf_counter()
     dt, last_loss = timed_run(args.warmup, n_need)
+    if rank == 0:
+        print(f"[bench] outside the timed steps: imports + model + batches {t_setup - T_START:.1f} s, captures + warm-up "
+              f"{time.perf_counter() - t_setup - dt:.1f} s", file=sys.stderr, flush=True)
     final_loss = float(last_loss.detach())  # after the timed region: the last step's loss (a replayed graph's static output)
     assert final_loss == final_loss and abs(final_loss) < 1e30, f"non-finite loss after the timed steps: {final_loss}"
     if args.dump_outputs and rank == 0:
@@ -613,7 +629,7 @@ def main():
                              communicators=(0 if comm is None else (1 if comm_grads is comm else 2)),
                              grad_wire=(buckets.wire if buckets is not None else "f32"),
                              bucket_mb=(round(buckets.flat[0].numel() * 4 / 2 ** 20, 1) if buckets is not None else 64))
-    if dp and buckets is not None and buckets.comm is not None and not selftest:
+    if args.full and dp and buckets is not None and buckets.comm is not None and not selftest:
         # one more step, eager, with an event pair around every bucket's exchange (EVERY rank runs it: the collectives need their
         # peers): when does each bucket leave, how long does it travel, and how long does the compute stream stand at the join
         # after the backward pass -- the part of the gradient exchange the backward pass did not hide
@@ -624,7 +640,9 @@ def main():
         rep = buckets.timing_report()
         if rep is not None:
             out["config"]["bucket_overlap"] = rep
-    if rank == 0 and not dp and not args.no_roofline:
+    # everything from here to the JSON line is --full: measurements and checks besides the headline figure, in runs of their own
+    extras = args.full and rank == 0 and not dp
+    if extras and not args.no_roofline:
         # (N > 1: an extra rank-0-only step would dead-lock the DDP / BatchNorm collectives; the kernels are the same)
         fwd, hbm, pair = roofline(model, data[args.warmup], ops)
         # `roofline` = the dominant kernel family BY TIME of the replayed step: the paired backward launches when they outweigh the
@@ -637,7 +655,7 @@ def main():
                 out["roofline_pair"] = pair
         if hbm is not None:
             out["roofline_hbm"] = hbm
-    if rank == 0 and not dp and not args.no_parity and args.modality == "video":
+    if extras and not args.no_parity and args.modality == "video":
         out["parity"] = parity_block(mode)
     def second_leg(leg_mode, description):
         """The SAME workload and step timed in another numerical mode (fewer steps, same protocol) + its parity block."""
@@ -660,7 +678,7 @@ def main():
         AF.invalidate_weight_cache()
         return res
 
-    legs_ok = rank == 0 and not dp and args.modality == "video" and not args.no_optimizer and not selftest
+    legs_ok = extras and args.modality == "video" and not args.no_optimizer and not selftest
     if legs_ok and mode != "bf16" and not args.no_second_leg:
         # the fastest arithmetic of this build, for comparison: bf16 operands in every contraction (8 significant bits: decoder
         # logits 7e-3 / CTC log-probabilities 4e-3 off the fp32 reference -- outside the north star's 1e-3 bound)
@@ -669,7 +687,7 @@ def main():
     if legs_ok and mode != "hpf" and args.hpf_leg:
         out["hpf"] = second_leg("hpf", "forward on split hi/lo bf16 planes everywhere (3 MFMAs per product, f32 activations), backward "
                                        "+ optimizer as the bf16 step")
-    if rank == 0 and not dp and not args.no_cpu_baseline:
+    if extras and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.modality, odim)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -4,14 +4,14 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out; mkdir -p $O
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 run() { name=$1; shift; timeout 900 "$@" > $O/$name.json 2> $O/$name.err; echo "$name rc=$? $(tail -c 300 $O/$name.json | head -c 0)$(python -c "
 import json,sys
 try:
     d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1]); print(d.get('ms_per_step'), d.get('value'))
 except Exception as e: print('?', e)
 ")"; }
-run r5_final_bench_default python bench.py --steps 20 --warmup 5
+run r5_final_bench_default python bench.py --full --steps 20 --warmup 5
 run r5_final_train_py python -u train.py --synthetic --synthetic-utterances 400 --steps 110 --time-last 30 --exp-dir "" --val-batches 0 --log-every 34
 run r5_final_bench_fixedA $B --fixed A --no-roofline --no-parity --no-bf16-leg
 run r5_final_bench_fixedB $B --fixed B --no-roofline --no-parity --no-bf16-leg
