@@ -15,12 +15,9 @@
 // consuming GEMMs through their device-side alpha (avsr_gemm alpha_dev).
 #include "prims.h"
 #include "avsr_hip.h"
+#include "ctc_common.h"  // LOG_ZERO, CTC_MAXSPL, CTC_PF, ctc_prepare_kernel, ctc_gather_kernel (shared with ctc_align.hip)
 
 namespace {
-
-constexpr float LOG_ZERO = -1e30f;
-constexpr int CTC_MAXSPL = 8;  // states per lane -> S <= 512, L <= 255
-constexpr int CTC_PF = 6;      // frames of emissions kept in flight ahead of the alpha / beta recursion
 
 AVSR_DEV float log_add(float a, float b) {
     const float m = fmaxf(a, b);
@@ -82,38 +79,6 @@ __global__ __launch_bounds__(256) void sub_row_scalar_kernel(const float* __rest
     const long r = blockIdx.x;
     const float l = lse[r];
     for (int v = threadIdx.x; v < V; v += 256) out[r * ld + v] = x[r * ld + v] - l;
-}
-
-// ---- per utterance: strip ignore_id from the padded label row, build the blank-interleaved sequence
-__global__ void ctc_prepare_kernel(const int64_t* __restrict__ labels, int Lmax, int ignore_id, int* __restrict__ ext,
-                                   int Smax, int* __restrict__ lens /* [B]: L_b */) {
-    const int b = blockIdx.x;
-    if (threadIdx.x != 0) return;
-    int L = 0;
-    int* e = ext + (long)b * Smax;
-    e[0] = 0;
-    for (int i = 0; i < Lmax; i++) {
-        const int64_t y = labels[(long)b * Lmax + i];
-        if (y == ignore_id) continue;
-        e[2 * L + 1] = (int)y;
-        e[2 * L + 2] = 0;
-        L++;
-    }
-    lens[b] = L;
-}
-
-// ---- lpg[b,t,s] = logit[b,t,ext[b,s]] - lse[b,t]
-template <class T>
-__global__ __launch_bounds__(256) void ctc_gather_kernel(const T* __restrict__ logits, long ld,
-                                                         const float* __restrict__ lse, const int* __restrict__ ext,
-                                                         const int* __restrict__ lens, float* __restrict__ lpg, int Tlen,
-                                                         int Smax) {
-    const long bt = blockIdx.x;
-    const int b = (int)(bt / Tlen);
-    const int S = 2 * lens[b] + 1;
-    const float l = lse[bt];
-    for (int s = threadIdx.x; s < S; s += 256)
-        lpg[bt * Smax + s] = Elem<T>::ld(logits + bt * ld + ext[(long)b * Smax + s]) - l;
 }
 
 // ---- alpha (blockIdx.y == 0) / beta (== 1) recursions: one wave per utterance, lane owns SPL contiguous states.
@@ -487,7 +452,7 @@ extern "C" int avsr_ctc_loss(const void* logits, int dtype, int64_t ld, const in
     int* lens = ext + (long)B * Smax;
     int rc = avsr_row_lse(logits, dtype, ld, lse, (int64_t)B * T, V, stream);
     if (rc) return rc;
-    AVSR_LAUNCH(ctc_prepare_kernel, dim3(B), dim3(64), 0, stream, labels, Lmax, ignore_id, ext, Smax, lens);
+    AVSR_LAUNCH(ctc_prepare_kernel, dim3(B), dim3(64), 0, stream, labels, Lmax, ignore_id, /*blank=*/0, ext, Smax, lens);
     if (dtype == 0)
         AVSR_LAUNCH((ctc_gather_kernel<float>), dim3(B * T), dim3(256), 0, stream, (const float*)logits, (long)ld, lse, ext, lens, lpg, T, Smax);
     else

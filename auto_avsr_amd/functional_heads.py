@@ -93,6 +93,25 @@ def ctc_loss(logits, labels, in_lens, ignore_id=-1):
     return CtcLossFn.apply(logits, labels, in_lens, ignore_id)
 
 
+def ctc_align(logits, labels, in_lens, blank=0, ignore_id=-1):
+    """CTC forced alignment (ctc.py:95-242) of logits [B,T,V] (f32 / bf16, possibly a [..., :V] view of a pitch-padded
+    buffer) against labels [B,L] padded with ignore_id.  Returns device tensors: ali int32 [B,T] (token id per frame,
+    ignore_id beyond in_lens[b]) and score f32 [B] (log-probability of the best path, -inf if infeasible).  No autograd."""
+    with torch.no_grad():
+        logits = logits.detach()
+        B, Tn, V = logits.shape
+        pit = _pitched_2d(logits, B * Tn, V) if logits.dtype in (torch.float32, torch.bfloat16) else None
+        if pit is None:
+            ld = padded_cols(V)
+            buf = torch.zeros(B * Tn, ld, dtype=torch.float32, device=logits.device)
+            buf[:, :V].copy_(logits.reshape(B * Tn, V))
+            pit = (buf, ld)
+        l2, ld = pit
+        lab = labels.reshape(B, -1).to(device=logits.device, dtype=torch.int64).contiguous()
+        lens = in_lens.to(device=logits.device, dtype=torch.int64).contiguous()
+        return ops.ctc_align(l2, ld, lab, lens, B, Tn, V, blank=int(blank), ignore_id=int(ignore_id))
+
+
 class CeSmoothFn(torch.autograd.Function):
     """label_smoothing_loss.py:41-63 (sum over tokens / B) + nets_utils.py:272-292 accuracy, on f32 logits
     [B,L,V].  Returns (loss, n_hits, n_valid) as device scalars."""

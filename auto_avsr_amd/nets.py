@@ -530,6 +530,31 @@ class CTC(nn.Module):
     def argmax(self, hs_pad):
         return torch.argmax(self._logits(hs_pad, False), dim=-1)
 
+    # ---- forced alignment (ctc.py:95-242): the Viterbi trellis runs on the device (csrc/ctc_align.hip)
+    def align(self, hs_pad, hlens, ys_pad, blank_id=0):
+        """Not in the reference: hidden states (B, T, D), lengths (B,), labels (B, L) padded with ignore_id -> device tensors
+        (ali int32 (B, T): token id per frame, ignore_id beyond hlens[b]; score f32 (B,): log-probability of the best path,
+        -inf and an all-ignore_id row where the labels do not fit the frames)."""
+        logits = self._logits(hs_pad, False)  # (B, T, V)
+        return AF.ctc_align(logits, ys_pad, hlens, blank=blank_id, ignore_id=self.ignore_id)
+
+    def forced_align(self, h, y, blank_id=0):
+        """ctc.py:95-158: hidden states (T, D) or (1, T, D), id sequence (L,) -> list of T token ids (python ints)."""
+        if h.dim() == 2:
+            h = h.unsqueeze(0)
+        y = torch.as_tensor(y, dtype=torch.int64).reshape(1, -1)
+        hlens = torch.tensor([h.shape[1]], dtype=torch.int64)
+        ali, _ = self.align(h, hlens, y, blank_id)
+        return ali[0].tolist()
+
+    def forced_align_batch(self, hs_pad, ys_pad, ilens, blank_id=0):
+        """ctc.py:160-242 as its code has it: hs_pad (Tmax, B, V) LOGITS, time-major; ys_pad (B, L) padded with ignore_id;
+        ilens (B,) -> list of B numpy int64 arrays, the b-th of length ilens[b]."""
+        ali, _ = AF.ctc_align(hs_pad.transpose(0, 1).contiguous(), torch.as_tensor(ys_pad), torch.as_tensor(ilens),
+                              blank=blank_id, ignore_id=self.ignore_id)
+        ali = ali.cpu().numpy().astype("int64")
+        return [ali[b, : int(t)] for b, t in enumerate(torch.as_tensor(ilens).tolist())]
+
 
 class LabelSmoothingLoss(nn.Module):
     """transformer/label_smoothing_loss.py:14-63 (KL divergence against the smoothed one-hot, summed, / batch)."""

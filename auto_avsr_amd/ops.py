@@ -556,6 +556,20 @@ def ctc_loss(logits, ld, labels, in_lens, B, T, V, want_grad=True, ignore_id=-1)
     return nll, grad
 
 
+def ctc_align(logits, ld, labels, in_lens, B, T, V, blank=0, ignore_id=-1):
+    """CTC forced alignment (ctc.py:95-242).  logits: [B*T, ld] (f32/bf16); labels int64 [B, Lmax]; in_lens int64 [B].
+    Returns ali int32 [B, T] (token id per frame, ignore_id for t >= in_lens[b]) and score f32 [B] (log-probability of the
+    best path; -inf = infeasible, its row of ali all ignore_id)."""
+    Lmax = labels.shape[1]
+    ws_bytes = call("avsr_ctc_align_workspace_bytes", B, T, Lmax)
+    ws = torch.empty(ws_bytes // 4 + 1, dtype=torch.float32, device=logits.device)
+    ali = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    score = torch.empty(B, dtype=torch.float32, device=logits.device)
+    call("avsr_ctc_align", _ptr(logits), dt(logits), ld, _ptr(labels), Lmax, ignore_id, _ptr(in_lens), blank, _ptr(ali),
+         _ptr(score), _ptr(ws), B, T, V, _stream(logits))
+    return ali, score
+
+
 def ce_smooth(logits, ld, target, V, smoothing, want_grad=True, ignore_id=-1):
     rows = target.numel()
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)

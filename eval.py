@@ -29,17 +29,26 @@ def parse_args(argv=None):
     p.add_argument("--decode-workers", type=int, default=1,
                    help="beam searches in flight at once (host threads + streams, one decoding session each); 1 = the reference's "
                         "one-utterance-at-a-time loop")
+    p.add_argument("--timestamps", type=str, default=None, metavar="PATH",
+                   help="write one JSON line per utterance with the word timestamps of its hypothesis (CTC forced alignment on the "
+                        "device, 40 ms per encoder frame): {utt, hyp, score, words: [{word, start, end}] or null}")
     return p.parse_args(argv)
 
 
-def run_test_loop(module, loader, device, log=None, decode_workers=1):
+def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps=None):
     """Trainer.test without Lightning: the module's own hooks over the loader (lightning.py:69-84,116-123).  decode_workers > 1:
-    utterances are taken in groups whose beam searches run concurrently (ModelModule.decode_many); same transcripts, same WER."""
+    utterances are taken in groups whose beam searches run concurrently (ModelModule.decode_many); same transcripts, same WER.
+    timestamps: path of a JSON-lines file that receives, per utterance, the word timestamps of its hypothesis (CTC forced
+    alignment on the encoder output the decoding already computed); without it nothing is aligned."""
+    import json
+
     import torch
 
     from lightning import compute_word_level_distance
 
     module.on_test_epoch_start()
+    records = [] if timestamps else None
+    module.timestamp_records = records  # test_step appends to it
     with torch.no_grad():
         if decode_workers <= 1:
             for i, sample in enumerate(loader):
@@ -52,7 +61,7 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1):
 
             def flush():
                 nonlocal done
-                for s, predicted in zip(group, module.decode_many([s["input"] for s in group], workers=decode_workers)):
+                for s, predicted in zip(group, module.decode_many([s["input"] for s in group], workers=decode_workers, records=records)):
                     actual = module.text_transform.post_process(s["target"])
                     module.total_edit_distance += compute_word_level_distance(actual, predicted)
                     module.total_length += len(actual.split())
@@ -67,6 +76,11 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1):
                     flush()
             if group:
                 flush()
+    module.timestamp_records = None
+    if timestamps:
+        with open(timestamps, "w", encoding="utf8") as f:
+            for i, rec in enumerate(records):
+                f.write(json.dumps({"utt": i, **rec}, ensure_ascii=False) + "\n")
     return module.on_test_epoch_end()
 
 
@@ -88,7 +102,7 @@ def cli_main(argv=None):
         args.synthetic_utterances = 4
     module = ModelModule(args)
     datamodule = DataModule(args)
-    if HAVE_LIGHTNING and not args.synthetic_utterances:
+    if HAVE_LIGHTNING and not args.synthetic_utterances and not args.timestamps:
         from pytorch_lightning import Trainer
 
         Trainer(num_nodes=1, devices=1, accelerator="gpu").test(model=module, datamodule=datamodule)
@@ -103,7 +117,7 @@ def cli_main(argv=None):
             SyntheticAVDataset(len(lens), args.modality, odim=module.model.odim, seed=2, lengths=lens), batch_size=None)
     else:
         loader = datamodule.test_dataloader()
-    wer = run_test_loop(module, loader, torch.device("cuda"), decode_workers=args.decode_workers,
+    wer = run_test_loop(module, loader, torch.device("cuda"), decode_workers=args.decode_workers, timestamps=args.timestamps,
                         log=lambda i, d, n: logging.info(f"utt {i}: running WER {d / max(n, 1):.4f} ({d}/{n} words)"))
     print(f"WER {wer:.4f} over {module.total_length} reference words")
     return wer

@@ -254,6 +254,16 @@ int64_t avsr_ctc_workspace_bytes(int B, int T, int Lmax);
 int avsr_ctc_loss(const void* logits, int dtype, int64_t ld, const int64_t* labels, int Lmax, int ignore_id,
                   const int64_t* in_lens, float* nll, void* grad, int64_t ldg, void* workspace, int B, int T,
                   int V, avsr_stream_t stream);
+/* CTC forced alignment (ctc_align.hip; ctc.py:95-242, CTC.forced_align / forced_align_batch): the best path of the
+ * blank-interleaved labels through the log-softmax of the logits.  Inputs as avsr_ctc_loss (labels padded with ignore_id
+ * anywhere, Lmax <= 255, T <= 32768).  ali int32 [B][T]: the token id emitted at each frame, ignore_id for t >= in_lens[b];
+ * score [B]: log-probability of that path.  Ties between predecessors go to the smallest step (stay, s-1, s-2) and the path
+ * ends in the last blank rather than the last label on a tie, as the reference's argmax order.  No labels: all blanks.
+ * Infeasible (fewer frames than labels + adjacent repeats, or in_lens[b] <= 0): score -inf and the whole row ignore_id. */
+int64_t avsr_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int avsr_ctc_align(const void* logits, int dtype, int64_t ld, const int64_t* labels, int Lmax, int ignore_id,
+                   const int64_t* in_lens, int blank, int32_t* ali, float* score, void* workspace, int B, int T,
+                   int V, avsr_stream_t stream);
 /* label-smoothing KL (label_smoothing_loss.py:41-63) per row + argmax hit (nets_utils.py:272-292);
  * grad = softmax - smoothed target (zero rows for ignored targets; pad columns [V, ldg) written as zeros), may be NULL */
 int avsr_ce_smooth(const void* logits, int dtype, int64_t ld, const int64_t* target, int ignore_id, int V,

@@ -194,21 +194,49 @@ class ModelModule(_Base):
         nbest_hyps = self.beam_search(enc_feat)
         nbest_hyps = [h.asdict() for h in nbest_hyps[: min(len(nbest_hyps), 1)]]
         predicted_token_id = torch.tensor(list(map(int, nbest_hyps[0]["yseq"][1:])))
+        self._last_decoded = (enc_feat, predicted_token_id)  # kept so that test_step can align the hypothesis without a second encoder pass
         return self.text_transform.post_process(predicted_token_id).replace("<eos>", "")
 
-    def decode_many(self, samples, workers=4):
+    # ---- word timestamps (not in the reference's scripts): CTC forced alignment (ctc.py:95-242) of a transcript on the device
+    def align_encoded(self, enc_feat, token_ids):
+        """Encoder output (T, D) + token ids of a transcript -> (word timestamps, log-probability of the best path).  <eos> and
+        blank ids are dropped from the transcript; (None, None) when nothing is left or it does not fit the frames."""
+        from auto_avsr_amd.alignment import word_timestamps
+
+        ids = [int(i) for i in token_ids if int(i) not in (self.model.eos, self.model.blank, -1)]
+        if not ids or enc_feat.shape[0] == 0:
+            return None, None
+        ali, score = self.model.ctc.align(enc_feat.unsqueeze(0), torch.tensor([enc_feat.shape[0]]), torch.tensor([ids]))
+        score = float(score[0])
+        if score == float("-inf"):
+            return None, None
+        return word_timestamps(ali[0], self.token_list, blank=self.model.blank), score
+
+    def align(self, sample, token_ids):
+        """Word timestamps ({"word", "start", "end"} in seconds, 40 ms per encoder frame) of a given transcript of `sample`."""
+        x = self.model.proj_encoder(self.model.frontend(sample.unsqueeze(0)))
+        enc_feat, _ = self.model.encoder(x, None)
+        return self.align_encoded(enc_feat.squeeze(0), token_ids)[0]
+
+    def _timestamp_record(self, enc_feat, token_ids, text):
+        words, score = self.align_encoded(enc_feat, token_ids)
+        return {"hyp": text, "score": score, "words": words}
+
+    def decode_many(self, samples, workers=4, records=None):
         """Not in the reference: the transcripts of several utterances, their beam searches running concurrently (one host
         thread + stream + decoding session per worker, BatchBeamSearch.forward_many); front-end / encoder one utterance at a
-        time as in `_decode`."""
+        time as in `_decode`.  records: a list that receives one word-timestamp record per utterance (eval.py --timestamps)."""
         encs = []
         for sample in samples:
             x = self.model.proj_encoder(self.model.frontend(sample.unsqueeze(0)))
             enc_feat, _ = self.model.encoder(x, None)
             encs.append(enc_feat.squeeze(0))
         out = []
-        for nbest in self.beam_search.forward_many(encs, workers=workers):
+        for enc, nbest in zip(encs, self.beam_search.forward_many(encs, workers=workers)):
             ids = torch.tensor(list(map(int, nbest[0].asdict()["yseq"][1:])))
             out.append(self.text_transform.post_process(ids).replace("<eos>", ""))
+            if records is not None:
+                records.append(self._timestamp_record(enc, ids, out[-1]))
         return out
 
     def forward(self, sample):
@@ -223,6 +251,8 @@ class ModelModule(_Base):
 
     def test_step(self, sample, sample_idx):
         predicted = self._decode(sample["input"])
+        if getattr(self, "timestamp_records", None) is not None:  # eval.py --timestamps: align the hypothesis just decoded
+            self.timestamp_records.append(self._timestamp_record(*self._last_decoded, predicted))
         actual = self.text_transform.post_process(sample["target"])
         self.total_edit_distance += compute_word_level_distance(actual, predicted)
         self.total_length += len(actual.split())
