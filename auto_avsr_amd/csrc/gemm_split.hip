@@ -413,6 +413,11 @@ extern "C" int avsr_gemm_f32s_nt(const float* A, int lda, const float* B, int ld
     return 0;
 }
 
+// conv3x3_c64_split.hip: the weights-in-registers, patch-staged persistent kernel for 3x3 / stride 1 / 64 -> 64 channels on split8 operands
+int avsr_conv3x3_c64_split_supported(int H, int W);
+int avsr_conv3x3_c64_split_launch(const void* x, const void* wq, float* y, void* y2, float* stats_part, int stats_rows,
+                                  const void* zero_page, int N, int H, int W, hipStream_t stream);
+
 // f32 implicit-GEMM convolution forward on split hi / lo bf16 planes: x[N,H,W,Cin] * wp[Cout][KH][KW][Cin] -> y[N,OH,OW,Cout]
 // (all f32, channels-last; Cin % 64 == 0; zero_page: >= 16 zero bytes in device memory)
 static int conv2d_f32s_impl(const float* x, const float* wp, float* y, const void* zero_page, int N, int H, int W, int Cin, int Cout, int KH,
@@ -444,6 +449,15 @@ static int conv2d_f32s_impl(const float* x, const float* wp, float* y, const voi
     // 22 (Cout >= 128) force a tile for A/B runs
     // round 6: stage-1 geometry (Cout = 64, >= 65 k output rows): 256 x 64 tiles on 8 waves, two blocks per CU: 293 -> 264 us
     // (profiles/r6_microbench_presplit.txt); the 256 x 128 tiles of the 128-channel stage measured slower (200 vs 171 us)
+    // stage-1 geometry proper (3x3 / stride 1 / 64 -> 64, x and wp pre-split): the patch-staged kernel of conv3x3_c64_split.hip
+    // from the output size on at which code 27 takes over below (knob 27: 1 = keep the tiled kernel, 2 = whatever the size)
+    if (tile == 23 && avsr_tune_knobs[21] == 0 && avsr_tune_knobs[27] != 1 && w_split && KH == 3 && KW == 3 && stride == 1 && pad_h == 1 &&
+        pad_w == 1 && Cin == 64 && Cout == 64 && ((long)N * OH * OW >= 65536 || avsr_tune_knobs[27] == 2) &&
+        avsr_conv3x3_c64_split_supported(H, W)) {
+        avsr_conv3x3_c64_split_launch(x, wp, y, y2, stats_part, stats_part ? stats_tiles : 0, zero_page, N, H, W, stream);
+        AVSR_CHECK_LAUNCH("conv2d_f32s");
+        return 0;
+    }
     if (tile == 23 && avsr_tune_knobs[21] == 0 && Cout == 64 && (long)N * OH * OW >= 65536) tile = 27;
     if (tile == 23 && avsr_tune_knobs[21] > 0) tile = avsr_tune_knobs[21];
     if (tile == 24 && avsr_tune_knobs[22] > 0) tile = avsr_tune_knobs[22];

@@ -371,7 +371,9 @@ int avsr_conv2d_f32s(const float* x, const float* wp, float* y, const void* zero
 /* the same convolution leaving the BatchNorm statistics of its output behind (frontend/resnet.py:82-98: every trunk convolution
  * feeds a BatchNorm in batch-statistics mode): row t of stats_part [stats_tiles >= ceil(rows / 128)][2][Cout] (need not be
  * initialised) = column sums / sums of squares of the stored values of output rows [128 t, 128 t + 128), from the epilogue -- no
- * statistics pass over y; finish with avsr_bn_finalize_parts (one rank) or avsr_bn_stats_parts + avsr_bn_finalize (cross-rank);
+ * statistics pass over y (kernels with other tiles -- 256-row tiles, the image bands of conv3x3_c64_split.hip -- fill one row per
+ * tile or group of tiles and zero the others: every row is written, and only the SUM of the rows is defined);
+ * finish with avsr_bn_finalize_parts (one rank) or avsr_bn_stats_parts + avsr_bn_finalize (cross-rank);
  * ws: 512 * C floats of scratch, zeros: >= C zero floats */
 int avsr_conv2d_f32s_stats(const float* x, const float* wp, float* y, const void* zero_page, int N, int H, int W, int Cin,
                            int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int tile, int w_split, void* y2,
@@ -421,7 +423,9 @@ int avsr_comm_reduce_scatter(int slot, const void* send, void* recv, int64_t cou
  * keep the tiled kernel; 2 = on whatever the grid size), 23 = deterministic mode (see auto_avsr_amd.functional.set_deterministic),
  * 24 = block-count target of avsr_conv2d_wgrad_bf16's k split (0 = by tile count: 512 / 1024 / 2048), 25 = rows per wave of
  * avsr_layernorm_bwd's dx blocks (0 = 1, or 2 with a column-sum output on > 1024 rows; tools/microbench_small.py), 26 = k split of
- * avsr_gemm_h16_nt with f32 atomics onto a ZEROED f32 C (probe: tools/microbench_splitk.py; slower at M = 1600).  Knobs 0..31 exist. */
+ * avsr_gemm_h16_nt with f32 atomics onto a ZEROED f32 C (probe: tools/microbench_splitk.py; slower at M = 1600), 27 = the patch-staged
+ * split-plane 3x3 kernel of conv3x3_c64_split.hip (0 = 3x3 / stride 1 / pad 1 / 64 -> 64 channel avsr_conv2d_f32s(_stats) calls on
+ * pre-split operands with >= 65536 output rows; 1 = off: keep the tiled kernel; 2 = on whatever the output size).  Knobs 0..31 exist. */
 int avsr_tune(int knob, int value);
 /* bf16 implicit-GEMM convolution on the tuned LDS-DMA kernel: dgrad = 0 forward, 1 data gradient (see
  * avsr_conv2d_fwd / avsr_conv2d_dgrad for the tensor conventions); gathered channel count % 64 == 0; stride 1 or 2

@@ -1,6 +1,7 @@
 """GPU ablation (round 5; round 6: tiles 27 - 30 = 256-row tiles on 8 waves): the split-plane convolution of ResNet stages 1 - 2 with the A tile converted to split8 in LDS (tiles 13 /
 14: what the mixed mode runs) against the same kernel on an A operand that ARRIVES pre-split (tiles 23 - 26: no conversion pass,
 one barrier per k-tile).  Timing only (the f32 input is read as if it were split8).  -> gpurun_out/microbench_presplit.json"""
+# (row l1 also times the patch-staged kernel of conv3x3_c64_split.hip: column c64split)
 import json
 import os
 import sys
@@ -42,7 +43,13 @@ for name, H, W, Cin, Cout, K, s, p in [("l1", 22, 22, 64, 64, 3, 1, 1), ("l2a", 
         def f(i, tile=tile):
             ops.call("avsr_conv2d_f32s_stats", ops._ptr(xs[i % 3]), ops._ptr(wp), ops._ptr(y), ops._ptr(ops.zero_page(dev)), N, H, W, Cin,
                      Cout, K, K, s, p, p, tile, 1, ops._ptr(y2), ops._ptr(st), st.shape[0], ops._stream(y))
-        res[f"t{tile}"] = round(timeit(f), 1)
+        ops.tune(27, 1)  # the tiled kernels themselves: keep code 23 off the patch-staged kernel
+        try:
+            res[f"t{tile}"] = round(timeit(f), 1)
+        finally:
+            ops.tune(27, 0)
+    if name == "l1":  # the patch-staged, weights-in-registers kernel of conv3x3_c64_split.hip (what code 23 runs at this size)
+        res["c64split"] = round(timeit(lambda i: f(i, 23)), 1)
     rows.append(dict(conv=name, gflop=round(2.0 * N * OH * OH * Cout * K * K * Cin / 1e9, 1), **res))
     print(rows[-1], flush=True)
 os.makedirs("gpurun_out", exist_ok=True)
