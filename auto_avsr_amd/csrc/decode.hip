@@ -487,6 +487,74 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int64_t* __restric
     }
 }
 
+// Input layer of the language model (ESPnet TransformerLM: embed -> Linear E->D -> LayerNorm -> ReLU -> x * sqrt(D) + pe) for the
+// last token of every hypothesis.  `table` [V][D] is embed followed by the Linear, contracted once at bind time, so the step
+// gathers a row instead of multiplying; block = row.  LayerNorm as torch computes it (mean, then the mean of the squared
+// deviations); st_out [M][1][2]: (sum, sum of squares) of the row written, for the LayerNorm-fused projection that follows.
+__global__ __launch_bounds__(256) void lm_input_kernel(const int64_t* __restrict__ last, const float* __restrict__ table,
+                                                       const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                                       const float* __restrict__ pe, float scale, int D, float* __restrict__ x,
+                                                       float* __restrict__ st_out) {
+    __shared__ float red[4];
+    const int m = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* row = table + (size_t)last[m] * D;
+    auto block_sum = [&](float v) -> float {
+        v = wave_sum(v);
+        __syncthreads();  // (the previous round's readers are done with red[])
+        if (lane == 0) red[wave] = v;
+        __syncthreads();
+        return (red[0] + red[1]) + (red[2] + red[3]);
+    };
+    float s = 0.f;
+    for (int n = threadIdx.x; n < D; n += 256) s += row[n];
+    const float mean = block_sum(s) / (float)D;
+    s = 0.f;
+    for (int n = threadIdx.x; n < D; n += 256) {
+        const float d = row[n] - mean;
+        s += d * d;
+    }
+    const float rstd = 1.0f / sqrtf(block_sum(s) / (float)D + eps);
+    float s1 = 0.f, s2 = 0.f;
+    for (int n = threadIdx.x; n < D; n += 256) {
+        const float v = fmaxf((row[n] - mean) * rstd * g[n] + b[n], 0.f) * scale + pe[n];
+        x[(size_t)m * D + n] = v;
+        s1 += v;
+        s2 += v * v;
+    }
+    s1 = block_sum(s1);
+    s2 = block_sum(s2);
+    if (threadIdx.x == 0) {
+        st_out[2 * m] = s1;
+        st_out[2 * m + 1] = s2;
+    }
+}
+
+// logp[row] = logits[row] - logsumexp(logits[row]) over the whole vocabulary (the language model's scores: no pre-beam of their
+// own, the selection reads them at the decoder's candidates); block = row
+__global__ __launch_bounds__(1024) void lm_logsoftmax_kernel(const float* __restrict__ logits, float* __restrict__ logp, long ld, int V) {
+    __shared__ float redf[16];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* x = logits + (size_t)row * ld;
+    float m = -INFINITY;
+    for (int i = tid; i < V; i += 1024) m = fmaxf(m, x[i]);
+    m = wave_max(m);
+    if (lane == 0) redf[wave] = m;
+    __syncthreads();
+    m = redf[0];
+    for (int w = 1; w < 16; w++) m = fmaxf(m, redf[w]);
+    __syncthreads();
+    float l = 0.f;
+    for (int i = tid; i < V; i += 1024) l += expf(x[i] - m);
+    l = wave_sum(l);
+    if (lane == 0) redf[wave] = l;
+    __syncthreads();
+    float lsum = 0.f;
+    for (int w = 0; w < 16; w++) lsum += redf[w];
+    const float lse = m + logf(lsum);
+    float* y = logp + (size_t)row * ld;
+    for (int i = tid; i < V; i += 1024) y[i] = x[i] - lse;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Top-S selection by radix select on the order-preserving integer image of the floats (keys in LDS).  The
 // digits are taken from key - min(key), most significant byte of the SPAN first: log-probabilities share sign and exponent,
@@ -659,7 +727,8 @@ __global__ __launch_bounds__(SEL_NT) void logsoftmax_prebeam_kernel(const float*
 // extended by one of its S candidates or by <eos> (scorers/ctc.py gives <eos> its complete-sequence probability whether
 // or not the pre-beam kept it; every other token outside the candidates carries the CTC scorer's LOGZERO and cannot
 // reach a beam of K <= n * (S - 1) -- the host refuses configurations where it could).  Arithmetic order as the python
-// form: ((w_dec * logp + w_len) + w_ctc * (log_psi - s_prev)) + score, f32.  ONE block: radix select of the
+// form: ((w_dec * logp [+ w_lm * lm_logp] + w_len) + w_ctc * (log_psi - s_prev)) + score, f32; the language model's term
+// (shallow fusion, scorers["lm"]) only with a session that carries one.  ONE block: radix select of the
 // K best values, then a rank sort of those K (value descending, entry ascending).
 struct SelectArgs {
     const float* logp;  // [n][ld] decoder log-probabilities
@@ -669,6 +738,8 @@ struct SelectArgs {
     int n, S, K;
     int eos, blank, has_len;
     float w_dec, w_ctc, w_len;
+    const float* lm_logp;  // [n][ld] language-model log-probabilities, NULL: no language model
+    float w_lm;
     int* sel;     // [K][4]: prev, tok, candidate column (-1: <eos> outside the candidates), spare
     float* selv;  // [K][4]: total, decoder term logp, ctc term (log_psi - s_prev), ctc log_psi
 };
@@ -711,6 +782,7 @@ __global__ __launch_bounds__(SEL_NT) void beam_select_kernel(SelectArgs a) {
         float dec, ctc_rel, log_psi, v = -INFINITY;
         if (decode(e, b, c, tok, dec, ctc_rel, log_psi)) {
             float w = a.w_dec * dec;
+            if (a.lm_logp) w = w + a.w_lm * a.lm_logp[(size_t)b * a.ld + tok];
             if (a.has_len) w = w + a.w_len;
             w = w + a.w_ctc * ctc_rel;
             v = w + a.score[b];
@@ -754,14 +826,15 @@ struct BeamBuf {
     int64_t* yseq;  // [beam][ldy]
     int* anc;       // [beam][ldy]: slot of the hypothesis' ancestor at position j (the row its K / V were written to)
     int64_t* last;  // [beam] last token
-    float* sc;      // [5][beam]: total, decoder sum, ctc sum, length sum, ctc log prefix probability s
+    float* sc;      // [6][beam]: total, decoder sum, ctc sum, length sum, ctc log prefix probability s, language-model sum
     float* r;       // [T][2][n] (pitch = current n)
 };
 
 // new hypothesis k = hypothesis prev[k] extended by tok[k]  (batch_beam_search.py:131-176 merge + select states)
 __global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf dst, int ldy, int beam, int L, int n_src, int K, int T, int S,
                                                           const int* __restrict__ sel, const float* __restrict__ selv,
-                                                          const float* __restrict__ r_new, float* __restrict__ host_row) {
+                                                          const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
+                                                          float* __restrict__ host_row) {
     const int k = blockIdx.x, tid = threadIdx.x;
     const int prev = sel[4 * k], tok = sel[4 * k + 1];
     int pos = sel[4 * k + 2];
@@ -781,6 +854,8 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf d
         dst.sc[2 * beam + k] = s_ctc;
         dst.sc[3 * beam + k] = s_len;
         dst.sc[4 * beam + k] = log_psi;
+        const float s_lm = src.sc[5 * beam + prev] + (lm_logp ? lm_logp[(size_t)prev * ld_lm + tok] : 0.f);
+        dst.sc[5 * beam + k] = s_lm;
         float* h = host_row + 8 * k;
         h[0] = (float)tok;
         h[1] = (float)prev;
@@ -788,7 +863,7 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf d
         h[3] = s_dec;
         h[4] = s_ctc;
         h[5] = s_len;
-        h[6] = 0.f;
+        h[6] = s_lm;
         h[7] = 0.f;
     }
     // CTC forward variables of (prev, candidate column pos): r_new [T][2][n_src][S] -> dst.r [T][2][K]
@@ -802,8 +877,8 @@ __global__ __launch_bounds__(256) void beam_keep_kernel(BeamBuf src, BeamBuf dst
         dst.yseq[(size_t)k * ldy + j] = src.yseq[(size_t)from * ldy + j];
         if (j < L - 1) dst.anc[(size_t)k * ldy + j] = src.anc[(size_t)from * ldy + j];
     }
-    if (tid < 5) dst.sc[tid * beam + k] = src.sc[tid * beam + from];
-    if (tid == 5) dst.last[k] = src.last[from];
+    if (tid < 6) dst.sc[tid * beam + k] = src.sc[tid * beam + from];
+    if (tid == 6) dst.last[k] = src.last[from];
     for (int i = tid; i < 2 * T; i += 256) dst.r[(size_t)i * keep.n + k] = src.r[(size_t)i * n_src + from];
 }
 
@@ -812,7 +887,7 @@ __global__ void beam_init_kernel(BeamBuf st, int beam, int T, int sos, const flo
     if (tid == 0) {
         st.yseq[0] = sos;
         st.last[0] = sos;
-        for (int i = 0; i < 5; i++) st.sc[i * beam] = 0.f;
+        for (int i = 0; i < 6; i++) st.sc[i * beam] = 0.f;
     }
     if (tid < 2 * T) st.r[tid] = r_init[tid];
 }
@@ -822,7 +897,25 @@ struct Layer {
     const float *n1g, *n1b, *wqkv, *bqkv, *wo, *bo, *n2g, *n2b, *wq2, *bq2, *wkv2, *bkv2, *wo2, *bo2, *n3g, *n3b, *w1, *b1, *w2, *b2;
 };
 
+struct LmLayer {
+    const float *n1g, *n1b, *wqkv, *bqkv, *wo, *bo, *n2g, *n2b, *w1, *b1, *w2, *b2;
+};
+
+// The language model a session may carry next to the decoder (avsr_beam_attach_lm): ESPnet's TransformerLM, pre-norm encoder layers
+// under the causal mask = the decoder's layers without source attention, on the same ancestry table.
+struct Lm {
+    int on = 0, D = 0, H = 0, FF = 0, nl = 0, pe_rows = 0;
+    float w = 0.f, scale = 0.f, eps = 0.f;
+    const float *table = nullptr, *eg = nullptr, *eb = nullptr, *pe = nullptr;  // [V][D] embed . Linear, its LayerNorm, positions
+    std::vector<LmLayer> layers;
+    const float *ang = nullptr, *anb = nullptr, *wout = nullptr, *bout = nullptr;
+    std::vector<float*> cache;  // per layer [Lmax][beam][3 D]
+    float *x = nullptr, *x1 = nullptr, *att = nullptr, *ff = nullptr, *part = nullptr, *stx = nullptr, *st1 = nullptr, *logits = nullptr,
+          *logp = nullptr;
+};
+
 struct Session {
+    Lm lm;
     int D, H, FF, V, nl, beam, S, sos, eos, blank, has_len;
     float w_dec, w_ctc, w_len, emb_scale, eps;
     const float *embed, *pe;
@@ -861,7 +954,7 @@ void carve(Session& s, Carver& c, int T, int Lmax) {
         s.st[i].yseq = c.take<int64_t>(beam * ldy);
         s.st[i].anc = c.take<int>(beam * ldy);
         s.st[i].last = c.take<int64_t>(beam);
-        s.st[i].sc = c.take<float>(5 * beam);
+        s.st[i].sc = c.take<float>(6 * beam);
         s.st[i].r = c.take<float>((size_t)2 * T * beam);
     }
     s.cache.resize(s.nl);
@@ -893,6 +986,21 @@ void carve(Session& s, Carver& c, int T, int Lmax) {
     s.sel = c.take<int>(4 * beam);
     s.selv = c.take<float>(4 * beam);
     s.host_dev = c.take<float>(8 * beam);
+    if (s.lm.on) {
+        Lm& m = s.lm;
+        const size_t Dl = m.D;
+        m.cache.resize(m.nl);
+        for (int l = 0; l < m.nl; l++) m.cache[l] = c.take<float>((size_t)Lmax * beam * 3 * Dl);
+        m.x = c.take<float>(beam * Dl);
+        m.x1 = c.take<float>(beam * Dl);
+        m.att = c.take<float>(beam * Dl);
+        m.ff = c.take<float>(beam * (size_t)m.FF);
+        m.part = c.take<float>((size_t)8 * beam * Dl);
+        m.stx = c.take<float>(beam * (Dl / 16) * 2);
+        m.st1 = c.take<float>(beam * (Dl / 16) * 2);
+        m.logits = c.take<float>(beam * (size_t)ldv);
+        m.logp = c.take<float>(beam * (size_t)ldv);
+    }
 }
 
 int gemm(const float* A, int lda, const float* B, int M, int N, int K, const float* bias, int act, const float* resid, int ldr, float* C,
@@ -900,6 +1008,17 @@ int gemm(const float* A, int lda, const float* B, int M, int N, int K, const flo
     return avsr_gemm_f32s_nt(A, lda, B, K, M, N, K, bias, act, nullptr, 0, 0, 1.f, 0.f, 0, nullptr, 1.f, nullptr, resid, 0, ldr, C, 0, ldc,
                              0, 1, 0, nullptr, 0, nullptr, 0, stream);
 }
+
+// Contraction lengths skinny16_kernel takes: K = 64 * nw * Z with nw waves of an instantiated block size, Z K slices (<= max_slices).
+// Returns Z, 0 when there is none.  The ONE statement of the rule on the device side (decode_native.skinny_len_ok on the host side).
+int skinny_slices(int K, int max_slices) {
+    auto ok_nw = [](int nw) { return nw >= 1 && nw <= 12 && (nw <= 4 || nw % 2 == 0); };  // the instantiated block sizes
+    if (K < 64 || K % 64) return 0;
+    for (int Z = 1; Z <= max_slices; Z++)
+        if (K % (64 * Z) == 0 && ok_nw(K / (64 * Z))) return Z;
+    return 0;
+}
+bool skinny_len_ok(int K, bool sliced_ok) { return skinny_slices(K, sliced_ok ? 8 : 1) != 0; }
 
 // per-row (sum, sum of squares) partials left by the producer of a [M][D] activation for the LayerNorm that consumes it
 struct RowStats {
@@ -913,10 +1032,8 @@ int skinny(const float* A, int lda, const float* W, int M, int N, int K, const f
            const RowStats* in, int act, const float* resid, int ldr, float* C, int ldc, RowStats* out, float* partial, hipStream_t stream) {
     // K slices across blocks when K exceeds the 16 waves x 64 columns of a block (the FFN's second contraction: K = 2048 /
     // 3072): partial sums, finished by rowsum_kernel
-    auto ok_nw = [](int nw) { return nw >= 1 && nw <= 12 && (nw <= 4 || nw % 2 == 0); };  // the instantiated block sizes
-    int Z = 1;
-    while (Z <= 8 && !(K % (64 * Z) == 0 && ok_nw(K / (64 * Z)))) Z++;
-    if (Z > 8 || (Z > 1 && (ln_g || act != 0 || !partial))) {
+    const int Z = skinny_slices(K, 8);
+    if (Z == 0 || (Z > 1 && (ln_g || act != 0 || !partial))) {
         avsr_set_error("beam_step: unsupported contraction length");
         return 1;
     }
@@ -944,6 +1061,41 @@ int skinny(const float* A, int lda, const float* W, int M, int N, int K, const f
     return 0;
 }
 
+__global__ void iota_rows_kernel(int* __restrict__ t, int len) {
+    for (int j = threadIdx.x; j < len; j += blockDim.x) t[(size_t)blockIdx.x * len + j] = blockIdx.x;
+}
+
+
+void lm_release(Lm& m) { m.on = 0; }
+
+// The language model's pass over the new position of the n running hypotheses: log-probabilities of the next token into lm.logp
+// [n][ldv].  Same shape as the decoder's pass without source attention: 2 + 5 launches per layer (6 with a sliced second FFN
+// contraction) + 1.
+int lm_step(Session& s, const BeamBuf& st, int n, int L, hipStream_t stream) {
+    Lm& m = s.lm;
+    const int D = m.D, beam = s.beam;
+    const float scale = 1.0f / sqrtf(64.f);
+    RowStats sx{m.stx, 1}, s1{m.st1, 0};
+    AVSR_LAUNCH(lm_input_kernel, dim3(n), dim3(256), 0, stream, (const int64_t*)st.last, m.table, m.eg, m.eb, m.eps, m.pe + (size_t)(L - 1) * D,
+                m.scale, D, m.x, sx.buf);
+    const int wv = L <= 64 ? 4 : (L <= 256 ? 8 : 16);
+    for (int l = 0; l < m.nl; l++) {
+        const LmLayer& w = m.layers[l];
+        float* row = m.cache[l] + (size_t)(L - 1) * beam * 3 * D;
+        int rc = skinny(m.x, D, w.wqkv, n, 3 * D, D, w.bqkv, w.n1g, w.n1b, m.eps, &sx, 0, nullptr, 0, row, 3 * D, nullptr, nullptr, stream);
+        if (rc) return rc;
+        AVSR_LAUNCH(dec_attn_kernel, dim3(n, m.H), dim3(64 * wv), (size_t)(L + 64 * wv) * sizeof(float), stream, (const float*)row, (long)3 * D,
+                    (const float*)m.cache[l], (long)beam * 3 * D, (long)3 * D, D, 2 * D, (const int*)st.anc, s.ldy, L, scale, m.att, (long)D);
+        if ((rc = skinny(m.att, D, w.wo, n, D, D, w.bo, nullptr, nullptr, 0.f, nullptr, 0, m.x, D, m.x1, D, &s1, nullptr, stream))) return rc;
+        if ((rc = skinny(m.x1, D, w.w1, n, m.FF, D, w.b1, w.n2g, w.n2b, m.eps, &s1, 1, nullptr, 0, m.ff, m.FF, nullptr, nullptr, stream))) return rc;
+        if ((rc = skinny(m.ff, m.FF, w.w2, n, D, m.FF, w.b2, nullptr, nullptr, 0.f, nullptr, 0, m.x1, D, m.x, D, &sx, m.part, stream))) return rc;
+    }
+    const int rc = skinny(m.x, D, m.wout, n, s.V, D, m.bout, m.ang, m.anb, m.eps, &sx, 0, nullptr, 0, m.logits, s.ldv, nullptr, nullptr, stream);
+    if (rc) return rc;
+    AVSR_LAUNCH(lm_logsoftmax_kernel, dim3(n), dim3(1024), 0, stream, (const float*)m.logits, m.logp, (long)s.ldv, s.V);
+    return 0;
+}
+
 }  // namespace
 
 #define DEC_TRY(call)             \
@@ -965,6 +1117,20 @@ extern "C" int avsr_decode_linear(const float* A, int lda, const float* W, int M
     if (rc != 0) return rc;
     AVSR_CHECK_LAUNCH("decode_linear");
     if (st_out_nt) *st_out_nt = out.nt;
+    return 0;
+}
+
+// The single-query attention of a decoding step on its own (the python-issued step of the language model, tests): query row b of
+// q [n][ldq] (H heads of 64) against keys / values kv[b][j] = kv + b * step_b + j * step_j (+ koff / voff), j < len; out [n][ldo].
+extern "C" int avsr_decode_attention(const float* q, int ldq, const float* kv, int64_t step_b, int64_t step_j, int koff, int voff, int n, int H,
+                                     int len, float* out, int ldo, int32_t* anc_scratch, hipStream_t stream) {
+    AVSR_REQUIRE(n >= 1 && H >= 1 && len >= 1 && len <= 8192, "decode_attention: bad sizes (1 <= len <= 8192)");
+    // dec_attn_kernel follows an ancestry table [n][len]: here every position of row b lives in slot b
+    AVSR_LAUNCH(iota_rows_kernel, dim3(n), dim3(256), 0, stream, anc_scratch, len);
+    const int wv = len <= 64 ? 4 : (len <= 256 ? 8 : 16);
+    AVSR_LAUNCH(dec_attn_kernel, dim3(n, H), dim3(64 * wv), (size_t)(len + 64 * wv) * sizeof(float), stream, q, (long)ldq, kv, (long)step_j, (long)step_b,
+                koff, voff, (const int*)anc_scratch, len, len, 1.0f / sqrtf(64.f), out, (long)ldo);
+    AVSR_CHECK_LAUNCH("decode_attention");
     return 0;
 }
 
@@ -998,7 +1164,42 @@ extern "C" int64_t avsr_beam_create(const int32_t* cfg, const float* fcfg, const
 }
 
 extern "C" int avsr_beam_destroy(int64_t h) {
-    delete reinterpret_cast<Session*>((intptr_t)h);
+    Session* s = reinterpret_cast<Session*>((intptr_t)h);
+    if (s) lm_release(s->lm);
+    delete s;
+    return 0;
+}
+
+// Attach a language model (shallow fusion, the reference's scorers["lm"] / weights["lm"]) to a session: ESPnet TransformerLM,
+// pre-norm, vocabulary = the decoder's.  Call between avsr_beam_create and avsr_beam_begin; the workspace grows by the model's share.
+// cfg: D, H, FF, n_layers, vocabulary, pe_rows
+// fcfg: weight of the model's log-probabilities, input scale (sqrt(D)), LayerNorm eps
+// w: table [V][D] (embed . encoder.embed.0, contracted by the caller), encoder.embed.1 gamma, beta, pe [pe_rows][D], then per layer
+// 12 pointers in the order of `struct LmLayer` (wqkv = rows of linear_q, linear_k, linear_v stacked), then after_norm gamma, beta,
+// decoder W [V][D], b
+extern "C" int avsr_beam_attach_lm(int64_t h, const int32_t* cfg, const float* fcfg, const void* const* w, int n_w) {
+    Session* sp = reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(sp != nullptr, "beam_attach_lm: no session");
+    Session& s = *sp;
+    // (the workspace of a session that has begun was carved without the model's share: its steps would run on buffers that do not exist)
+    AVSR_REQUIRE(s.T == 0, "beam_attach_lm: the session has begun an utterance (attach between avsr_beam_create and the first avsr_beam_begin)");
+    const int D = cfg[0], H = cfg[1], FF = cfg[2], nl = cfg[3];
+    AVSR_REQUIRE(nl >= 1 && n_w == 4 + 12 * nl + 4, "beam_attach_lm: pointer count does not match the layer count");
+    AVSR_REQUIRE(D >= 64 && D == 64 * H && skinny_len_ok(D, false), "beam_attach_lm: unsupported width (d_k = 64, D / 64 an instantiated block size)");
+    AVSR_REQUIRE(FF >= 64 && skinny_len_ok(FF, true), "beam_attach_lm: unsupported feed-forward width");
+    AVSR_REQUIRE(cfg[4] == s.V, "beam_attach_lm: the language model's vocabulary differs from the decoder's");
+    AVSR_REQUIRE(cfg[5] >= 2, "beam_attach_lm: bad position table");
+    lm_release(s.lm);
+    Lm& m = s.lm;
+    m.D = D; m.H = H; m.FF = FF; m.nl = nl; m.pe_rows = cfg[5];
+    m.w = fcfg[0]; m.scale = fcfg[1]; m.eps = fcfg[2];
+    const float* const* p = reinterpret_cast<const float* const*>(w);
+    m.table = p[0]; m.eg = p[1]; m.eb = p[2]; m.pe = p[3];
+    m.layers.resize(nl);
+    static_assert(sizeof(LmLayer) == 12 * sizeof(void*), "LmLayer is 12 pointers");
+    for (int l = 0; l < nl; l++) memcpy(&m.layers[l], p + 4 + 12 * l, sizeof(LmLayer));
+    m.ang = p[4 + 12 * nl]; m.anb = p[5 + 12 * nl]; m.wout = p[6 + 12 * nl]; m.bout = p[7 + 12 * nl];
+    m.on = 1;
     return 0;
 }
 
@@ -1015,6 +1216,7 @@ extern "C" int avsr_beam_begin(int64_t h, const float* memory, int T, const floa
                                int64_t ws_bytes, int Lmax, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
     AVSR_REQUIRE(T >= 1 && Lmax >= 1 && Lmax + 1 <= s.pe_rows, "beam_begin: bad lengths (position table too short?)");
+    AVSR_REQUIRE(!s.lm.on || Lmax + 1 <= s.lm.pe_rows, "beam_begin: the language model's position table is too short");
     Carver c{reinterpret_cast<char*>(ws)};
     carve(s, c, T, Lmax);
     AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin: workspace too small");
@@ -1034,7 +1236,8 @@ extern "C" int avsr_beam_begin(int64_t h, const float* memory, int T, const floa
 
 // One decoding step for the n running hypotheses (all of length L): decoder pass over the new position, pre-beam, CTC
 // prefix scores, top-K, new beam state.  host_out [K][8] f32: token, parent, total score, decoder / ctc / length-bonus
-// sums, 0, 0 -- valid on return (the call synchronises the stream).  Returns K through n_out.
+// sums, language-model sum (0 without one), 0 -- valid on return (the call synchronises the stream).  Returns K through n_out.
+// With a language model attached its pass is issued first, in line on the same stream.
 extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
     AVSR_REQUIRE(s.n >= 1 && s.L <= s.Lmax, "beam_step: no running hypotheses / maximum length reached");
@@ -1042,6 +1245,7 @@ extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_
     BeamBuf& st = s.st[s.cur];
     BeamBuf& nx = s.st[s.cur ^ 1];
     const float scale = 1.0f / sqrtf(64.f);
+    if (s.lm.on) DEC_TRY(lm_step(s, st, n, L, stream));
     // embedding of the last token at position L - 1 (transformer_decoder.py:186-189, embedding.py:78-87) + its row statistics
     RowStats sx{s.stx, 1}, s1{s.st1, 0}, s2{s.st2, 0};
     AVSR_LAUNCH(dec_embed_kernel, dim3(n), dim3(256), 0, stream, (const int64_t*)st.last, s.embed, s.pe + (size_t)(L - 1) * D, s.emb_scale, D,
@@ -1070,10 +1274,10 @@ extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_
     const int NE = n * (s.S + 1);
     const int K = beam;  // n * V >= beam always; the viable entries n * (S - 1) >= beam by the create-time check
     SelectArgs a{s.logp, (long)s.ldv, s.cand, s.psi, s.psi_eos, st.sc + 4 * beam, st.sc, n, s.S, K, s.eos, s.blank, s.has_len,
-                 s.w_dec, s.w_ctc, s.w_len, s.sel, s.selv};
+                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv};
     AVSR_LAUNCH(beam_select_kernel, dim3(1), dim3(SEL_NT), (size_t)(2 * NE + K + n * s.S + n) * 4, stream, a);
     AVSR_LAUNCH(beam_update_kernel, dim3(K), dim3(256), 0, stream, st, nx, s.ldy, beam, L, n, K, s.T, s.S, (const int*)s.sel,
-                (const float*)s.selv, (const float*)s.r_new, s.host_dev);
+                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, s.host_dev);
     AVSR_CHECK_LAUNCH("beam_step");
     const int e = avsr_copy_to_host_sync(host_out, s.host_dev, (size_t)K * 8 * sizeof(float), stream);
     if (e != 0) {

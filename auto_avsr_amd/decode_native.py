@@ -20,6 +20,15 @@ from . import _lib, ops
 MAX_BEAM = 128
 
 
+def skinny_len_ok(K, sliced_ok):
+    """Contraction lengths the linear kernel of a decoding step takes (csrc/decode.hip skinny_slices): K = 64 * nw * Z with nw an
+    instantiated block size (waves of 64 columns of K) and, where the call site allows K slices, Z <= 8."""
+    def block_ok(nw):
+        return 1 <= nw <= 12 and (nw <= 4 or nw % 2 == 0)
+
+    return K >= 64 and K % 64 == 0 and any(K % (64 * z) == 0 and block_ok(K // (64 * z)) for z in range(1, 9 if sliced_ok else 2))
+
+
 def _f32(t):
     t = t.detach()
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
@@ -31,13 +40,14 @@ class NativeBeam:
     def __init__(self, bs):
         self.bs = bs
         self.handle = 0
+        self.lib = None  # the library object that made `handle` (a session is destroyed by the library that created it)
         self.key = None
         self.keep_alive = []
 
     def __del__(self):
         try:
             if self.handle:
-                _lib.lib().call("avsr_beam_destroy", self.handle)
+                self.lib.call("avsr_beam_destroy", self.handle)
         except Exception:
             pass
 
@@ -52,8 +62,17 @@ class NativeBeam:
             return False
         if "decoder" not in full or not isinstance(full["decoder"], TransformerDecoder):
             return False
-        if set(full) - {"decoder", "length_bonus"}:
+        if set(full) - {"decoder", "length_bonus", "lm"}:
             return False
+        if "lm" in full:  # shallow fusion: this build's TransformerLM in a geometry the session takes, nothing else
+            from .lm import TransformerLM
+
+            if not isinstance(full["lm"], TransformerLM) or not full["lm"].native_ok(bs.n_vocab):
+                return False
+            # the step's pre-beam ranks the decoder's log-probabilities alone: with a language model "full" (decoder + LM) is another
+            # candidate set (without one the length bonus is a per-row constant and the two keys select alike)
+            if bs.pre_beam_score_key != "decoder":
+                return False
         if "length_bonus" in full and not isinstance(full["length_bonus"], LengthBonus):
             return False
         if not bs.do_pre_beam or bs.pre_beam_score_key not in ("decoder", "full") or bs.weights["decoder"] <= 0:
@@ -64,11 +83,7 @@ class NativeBeam:
         FF = lay.feed_forward.w_1.out_features
         if dec.output_layer is None or not dec.normalize_before or D != 64 * H or FF % 64:
             return False
-
-        def block_ok(nw):  # the block sizes csrc/decode.hip instantiates (waves of 64 columns of K)
-            return 1 <= nw <= 12 and (nw <= 4 or nw % 2 == 0)
-
-        if not block_ok(D // 64) or not any(FF % (64 * z) == 0 and block_ok(FF // (64 * z)) for z in range(1, 9)):
+        if not skinny_len_ok(D, False) or not skinny_len_ok(FF, True):
             return False
         beam, S = bs.beam_size, bs.pre_beam_size
         return 2 <= beam <= MAX_BEAM and beam <= S - 1 and beam * (S + 1) <= 8192
@@ -77,19 +92,25 @@ class NativeBeam:
     def _bind(self, dev, min_pos):
         bs = self.bs
         dec = bs.full_scorers["decoder"]
-        params = list(dec.parameters())
+        lm = bs.full_scorers.get("lm")
+        params = list(dec.parameters()) + (list(lm.parameters()) if lm is not None else [])
         pos = dec.embed[1]
         pe = _f32(pos.table(max(pos.pe.size(1), min_pos), dev))
+        if lm is not None:
+            lm_pos = lm.encoder.embed[4]
+            lm_pe = _f32(lm_pos.table(max(lm_pos.pe.size(1), min_pos), dev))
         # (FusedAdamW updates parameters through raw pointers without bumping `_version`: the optimizer-step generation of the
         # weight caches is part of the key, so the stacked copies below are rebuilt after native training steps too)
         from . import functional as AF
 
         key = (str(dev), pe.data_ptr(), pe.shape[0], AF._wgen["gen"]) + tuple((p.data_ptr(), p._version) for p in params)
+        if lm is not None:
+            key += (lm_pe.data_ptr(), lm_pe.shape[0], float(bs.weights["lm"]))
         if key == self.key:
             return
         L = _lib.lib()
         if self.handle:
-            L.call("avsr_beam_destroy", self.handle)
+            self.lib.call("avsr_beam_destroy", self.handle)
             self.handle = 0
         lay0 = dec.decoders[0]
         D, H, FF = lay0.size, lay0.self_attn.h, lay0.feed_forward.w_1.out_features
@@ -113,24 +134,50 @@ class NativeBeam:
                          _f32(d.norm3.weight), _f32(d.norm3.bias), _f32(ff.w_1.weight), _f32(ff.w_1.bias), _f32(ff.w_2.weight),
                          _f32(ff.w_2.bias)]
             keep += [_f32(dec.after_norm.weight), _f32(dec.after_norm.bias), _f32(dec.output_layer.weight), _f32(dec.output_layer.bias)]
+            if lm is not None:  # (after the decoder's pointers: avsr_beam_attach_lm's list)
+                keep += self._lm_weights(lm, lm_pe)
             bs._native_weights = (key, keep)
         assert all(t.device == keep[0].device for t in keep)
+        n_dec = 2 + 20 * len(dec.decoders) + 4
+        keep_lm, keep_dec = keep[n_dec:], keep[:n_dec]
         has_len = int("length_bonus" in bs.full_scorers)
         cfg = (ctypes.c_int32 * 12)(D, H, FF, V, len(dec.decoders), bs.beam_size, bs.pre_beam_size, bs.sos, bs.eos,
                                     bs.part_scorers["ctc"].blank, has_len, pe.shape[0])
         fcfg = (ctypes.c_float * 5)(bs.weights["decoder"], bs.weights["ctc"], bs.weights.get("length_bonus", 0.0) if has_len else 0.0,
                                     pos.xscale, dec.decoders[0].norm1.eps)
-        ptrs = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+        ptrs = (ctypes.c_void_p * len(keep_dec))(*[t.data_ptr() for t in keep_dec])
         h = L.call("avsr_beam_create", ctypes.cast(cfg, ctypes.c_void_p), ctypes.cast(fcfg, ctypes.c_void_p),
-                   ctypes.cast(ptrs, ctypes.c_void_p), len(keep))
+                   ctypes.cast(ptrs, ctypes.c_void_p), len(keep_dec))
         if not h:
             raise _lib.AvsrLibraryError("avsr_beam_create: " + L.cdll.avsr_last_error().decode())
-        self.handle, self.key, self.keep_alive = h, key, keep
+        if lm is not None:
+            lcfg = (ctypes.c_int32 * 6)(lm.att_unit, lm.head, lm.unit, lm.layer, lm.n_vocab, lm_pe.shape[0])
+            lfcfg = (ctypes.c_float * 3)(bs.weights["lm"], lm_pos.xscale, lm.encoder.encoders[0].norm1.eps)
+            lptrs = (ctypes.c_void_p * len(keep_lm))(*[t.data_ptr() for t in keep_lm])
+            try:
+                L.call("avsr_beam_attach_lm", h, ctypes.cast(lcfg, ctypes.c_void_p), ctypes.cast(lfcfg, ctypes.c_void_p),
+                       ctypes.cast(lptrs, ctypes.c_void_p), len(keep_lm))
+            except Exception:
+                L.call("avsr_beam_destroy", h)
+                raise
+        self.handle, self.lib, self.key, self.keep_alive = h, L, key, keep
         self.V, self.pe_rows = V, pe.shape[0]
         pin = dev.type == "cuda"
         self.host = torch.empty(MAX_BEAM * 8, dtype=torch.float32, pin_memory=pin)
         self.host_np = self.host.numpy().reshape(MAX_BEAM, 8)
         self.yseq_host = None
+
+    @staticmethod
+    def _lm_weights(lm, lm_pe):
+        _, table, qkv = lm.derived()
+        ln = lm.encoder.embed[1]
+        out = [table, _f32(ln.weight), _f32(ln.bias), lm_pe]
+        for e, (wqkv, bqkv) in zip(lm.encoder.encoders, qkv):
+            sa, ff = e.self_attn, e.feed_forward
+            out += [_f32(e.norm1.weight), _f32(e.norm1.bias), wqkv, bqkv, _f32(sa.linear_out.weight), _f32(sa.linear_out.bias),
+                    _f32(e.norm2.weight), _f32(e.norm2.bias), _f32(ff.w_1.weight), _f32(ff.w_1.bias), _f32(ff.w_2.weight), _f32(ff.w_2.bias)]
+        an = lm.encoder.after_norm
+        return out + [_f32(an.weight), _f32(an.bias), _f32(lm.decoder.weight), _f32(lm.decoder.bias)]
 
     # ------------------------------------------------------------------------------------------------ the search
     @torch.no_grad()
@@ -159,8 +206,8 @@ class NativeBeam:
                nws, maxlen, stream)
         n_out = ctypes.c_int(0)
         host_ptr, n_ptr = self.host.data_ptr(), ctypes.cast(ctypes.pointer(n_out), ctypes.c_void_p)
-        names = ["decoder"] + (["length_bonus"] if "length_bonus" in bs.full_scorers else []) + ["ctc"]
-        col = {"decoder": 3, "ctc": 4, "length_bonus": 5}
+        names = ["decoder"] + [k for k in ("lm", "length_bonus") if k in bs.full_scorers] + ["ctc"]
+        col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6}
         eos = bs.eos
         ended, best, best_len = [], -math.inf, {}
 

@@ -32,6 +32,11 @@ def parse_args(argv=None):
     p.add_argument("--timestamps", type=str, default=None, metavar="PATH",
                    help="write one JSON line per utterance with the word timestamps of its hypothesis (CTC forced alignment on the "
                         "device, 40 ms per encoder frame): {utt, hyp, score, words: [{word, start, end}] or null}")
+    p.add_argument("--lm-path", type=str, default=None,
+                   help="state dict of a Transformer language model (ESPnet TransformerLM layout) for shallow fusion in the beam search")
+    p.add_argument("--lm-conf", type=str, default=None,
+                   help="JSON file with the language model's layer / unit / att_unit / head / embed_unit (default: 16 / 2048 / 512 / 8 / 128)")
+    p.add_argument("--lm-weight", type=float, default=0.0, help="weight of the language model's log-probabilities (0: no fusion)")
     return p.parse_args(argv)
 
 

@@ -512,6 +512,17 @@ int avsr_ctc_prefix_score(const float* logp, int T, int V, int ldv, const float*
  * all f32 device pointers that outlive the session.  Returns an opaque handle, 0 on an unsupported configuration. */
 int64_t avsr_beam_create(const int32_t* cfg, const float* fcfg, const void* const* w, int n_w);
 int avsr_beam_destroy(int64_t handle);
+/* Language-model shallow fusion (the reference's scorers["lm"] / weights["lm"]): attach an ESPnet-layout pre-norm TransformerLM to a
+ * session, between avsr_beam_create and avsr_beam_begin.  avsr_beam_workspace_bytes then includes the model's share (per layer a
+ * [Lmax][beam][3 D] cache), every step adds weight * log p_lm(token) at the entries it scores (the pre-beam candidates and <eos>)
+ * and carries the running sum in column 6 of the step's host record.
+ * cfg: D, H, FF, n_layers, vocabulary, pe_rows
+ * fcfg: weight, input scale sqrt(D), LayerNorm eps
+ * w: table [V][D] = embed followed by encoder.embed.0 (contracted by the caller), encoder.embed.1 gamma, beta, position table
+ * [pe_rows][D], per layer {norm1 g, b, W_qkv [3D][D], b_qkv, W_o, b_o, norm2 g, b, W_1 [FF][D], b_1, W_2 [D][FF], b_2}, after_norm g, b,
+ * decoder W [V][D], b; all f32 device pointers that outlive the session.  Requires D = 64 H with D / 64 and FF / 64 (or a slice of it)
+ * among the block sizes of the step's linear kernel, and the decoder's vocabulary; refused once the session has begun an utterance. */
+int avsr_beam_attach_lm(int64_t handle, const int32_t* cfg, const float* fcfg, const void* const* w, int n_w);
 int64_t avsr_beam_workspace_bytes(int64_t handle, int T, int Lmax);
 /* the linear layer of a decoding step on its own: C = act(LN?(A) W^T + bias) + resid for M <= 128 rows (transformer_decoder.py:84-126
  * on one position per hypothesis); st_in [M][st_in_nt][2] per-row (sum, sum of squares) partials of A when ln_g != NULL;
@@ -520,11 +531,16 @@ int64_t avsr_beam_workspace_bytes(int64_t handle, int T, int Lmax);
 int avsr_decode_linear(const float* A, int lda, const float* W, int M, int N, int K, const float* bias, const float* ln_g,
                        const float* ln_b, float eps, const float* st_in, int st_in_nt, int act, const float* resid, int ldr,
                        float* C, int ldc, float* st_out, int* st_out_nt, float* partial, avsr_stream_t stream);
+/* the single-query attention of a decoding step on its own (attention.py:59-104 with one query row per hypothesis, d_k = 64): query
+ * row b of q [n][ldq] against its own keys / values kv + b * step_b + j * step_j (+ koff / voff), j < len <= 8192; out [n][ldo];
+ * anc_scratch: n * len ints of scratch */
+int avsr_decode_attention(const float* q, int ldq, const float* kv, int64_t step_b, int64_t step_j, int koff, int voff, int n, int H,
+                          int len, float* out, int ldo, int32_t* anc_scratch, avsr_stream_t stream);
 /* new utterance: memory [T][D] f32 encoder output, ctc_logp [T][ld_ctc] f32 log-softmax of the CTC head, r_init [T][2] CTC
  * state of the empty prefix (ctc_prefix_score.py:60-66), workspace of avsr_beam_workspace_bytes(handle, T, Lmax) */
 int avsr_beam_begin(int64_t handle, const float* memory, int T, const float* ctc_logp, int ld_ctc, const float* r_init,
                     void* workspace, int64_t workspace_bytes, int Lmax, avsr_stream_t stream);
-/* one step for all running hypotheses; host_out [K][8] f32 = {token, parent, total, decoder sum, ctc sum, length sum, 0, 0},
+/* one step for all running hypotheses; host_out [K][8] f32 = {token, parent, total, decoder sum, ctc sum, length sum, language-model sum (0 without one), 0},
  * valid on return (synchronises the stream); K through n_out */
 int avsr_beam_step(int64_t handle, float* host_out, int* n_out, avsr_stream_t stream);
 /* drop the hypotheses not listed (ended ones, batch_beam_search.py:178-206); keep: ascending indices into the current beam */

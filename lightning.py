@@ -239,15 +239,31 @@ class ModelModule(_Base):
                 records.append(self._timestamp_record(enc, ids, out[-1]))
         return out
 
+    def _make_beam_search(self):
+        """The search of `forward` / the test loop; `args.lm_path`, `args.lm_conf`, `args.lm_weight` (eval.py --lm-path / --lm-conf /
+        --lm-weight), when present, put a Transformer LM into the reference's `lm` slot (shallow fusion).  The LM is loaded once."""
+        args = getattr(self, "args", None)
+        lm_path, lm_weight = getattr(args, "lm_path", None), float(getattr(args, "lm_weight", 0.0) or 0.0)
+        if not lm_path or lm_weight == 0.0:
+            return get_beam_search_decoder(self.model, self.token_list)
+        cached = getattr(self, "_lm", None)
+        if cached is None or cached[0] != (lm_path, getattr(args, "lm_conf", None)):
+            from auto_avsr_amd.lm import TransformerLM
+
+            lm = TransformerLM.from_files(len(self.token_list), lm_path, getattr(args, "lm_conf", None),
+                                          device=next(self.model.parameters()).device)
+            cached = self._lm = ((lm_path, getattr(args, "lm_conf", None)), [lm])  # (in a list: not a sub-module, not in state_dict)
+        return get_beam_search_decoder(self.model, self.token_list, rnnlm=cached[1][0], lm_weight=lm_weight)
+
     def forward(self, sample):
-        self.beam_search = get_beam_search_decoder(self.model, self.token_list)
+        self.beam_search = self._make_beam_search()
         return self._decode(sample)
 
     def on_test_epoch_start(self):
         self.total_length = 0
         self.total_edit_distance = 0
         self.text_transform = TextTransform()
-        self.beam_search = get_beam_search_decoder(self.model, self.token_list)
+        self.beam_search = self._make_beam_search()
 
     def test_step(self, sample, sample_idx):
         predicted = self._decode(sample["input"])
@@ -267,15 +283,32 @@ class ModelModule(_Base):
 def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight=0.1, lm_weight=0.0,
                             beam_size=40):
     """lightning.py:126-158: decoder (1 - ctc_weight) + CTC prefix scorer (ctc_weight) + length bonus (penalty), beam 40,
-    pre-beam on the decoder scores.  No language model is shipped with the reference (`scorers["lm"] = None`)."""
+    pre-beam on the decoder scores.  No language model is shipped with the reference (`scorers["lm"] = None`); its `lm` slot is
+    served here: rnnlm = an auto_avsr_amd.lm.TransformerLM, or the path of its state dict (ESPnet layout, optionally under a
+    `predictor.` prefix) with rnnlm_conf = a dict or the path of a JSON file giving layer / unit / att_unit / head / embed_unit;
+    lm_weight = its weight in the score (shallow fusion).  lm_weight == 0 or rnnlm None: the search without a language model."""
     from espnet.nets.batch_beam_search import BatchBeamSearch
     from espnet.nets.scorers.length_bonus import LengthBonus
 
-    if rnnlm is not None or lm_weight != 0.0:
-        raise NotImplementedError("language-model fusion is not part of the reference's released configuration")
+    lm = None
+    if rnnlm is not None and lm_weight != 0.0:
+        from auto_avsr_amd.lm import TransformerLM
+
+        if isinstance(rnnlm, TransformerLM):
+            lm = rnnlm
+        elif isinstance(rnnlm, (str, bytes)) or hasattr(rnnlm, "__fspath__"):
+            lm = TransformerLM.from_files(len(token_list), rnnlm, rnnlm_conf, device=next(model.parameters()).device)
+        else:
+            raise TypeError("rnnlm: a TransformerLM or the path of its state dict")
+        if lm.n_vocab != len(token_list):
+            raise ValueError(f"the language model's vocabulary ({lm.n_vocab}) is not the token list's ({len(token_list)})")
+    elif lm_weight != 0.0:
+        import warnings
+
+        warnings.warn(f"lm_weight={lm_weight} without a language model (rnnlm is None): the search runs without fusion")
     sos = eos = model.odim - 1
     scorers = model.scorers()
-    scorers["lm"] = None
+    scorers["lm"] = lm
     scorers["length_bonus"] = LengthBonus(len(token_list))
     weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight, "length_bonus": penalty}
     return BatchBeamSearch(beam_size=beam_size, vocab_size=len(token_list), weights=weights, scorers=scorers, sos=sos, eos=eos,

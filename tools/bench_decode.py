@@ -21,7 +21,14 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--beam", type=int, default=40)
     ap.add_argument("--many", type=int, default=16, help="utterances of the concurrent-decoding rows (BatchBeamSearch.forward_many)")
+    ap.add_argument("--lm", action="store_true",
+                    help="shallow fusion rows instead of the default ones: a Transformer LM of 16 layers x 512 (8 heads, FF 2048, E 128, synthetic "
+                         "weights), lm_weight 0.3 -- native step, python-issued step with the "
+                         "cached TransformerLM, python-issued step with a plain-torch LM as a foreign scorer (what a build without the LM slot "
+                         "can do)")
     args = ap.parse_args()
+    if args.lm:
+        return main_lm(args)
     import lightning
     from synth import synth_batch, synth_state_dict
 
@@ -98,6 +105,135 @@ def main():
     decoding.NATIVE_BEAM = True
     print(json.dumps({"metric": "decode throughput, video E2E 250M, hybrid CTC/attention beam search (lightning.py:54-64,126-158)",
                       "reference_cpu": "2.12 s per 4 s utterance (T = 100), 8 host cores, BASELINE.md section 2",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+class PlainTorchLM:
+    """The LM of auto_avsr_amd.lm.TransformerLM in plain torch, without a cache, as a FOREIGN full scorer: the only way to fuse a
+    language model without the `lm` slot -- the search then runs the python-issued step and the LM re-runs the whole prefix of every
+    hypothesis at every step."""
+
+    def __init__(self, lm):
+        self.sd = {k: v.detach().float() for k, v in lm.state_dict().items()}
+        self.D, self.H, self.nl = lm.att_unit, lm.head, lm.layer
+        self.pos = lm.encoder.embed[4]
+
+    @torch.no_grad()
+    def batch_score(self, ys, states, xs):
+        F, sd, D, H = torch.nn.functional, self.sd, self.D, self.H
+        n, L = ys.shape
+        x = F.linear(F.embedding(ys, sd["embed.weight"]), sd["encoder.embed.0.weight"], sd["encoder.embed.0.bias"])
+        x = F.layer_norm(x, (D,), sd["encoder.embed.1.weight"], sd["encoder.embed.1.bias"], 1e-12)
+        x = torch.relu(x) * self.pos.xscale + self.pos.table(L, ys.device)
+        mask = torch.ones(L, L, dtype=torch.bool, device=ys.device).tril()
+        for i in range(self.nl):
+            p = f"encoder.encoders.{i}."
+            h = F.layer_norm(x, (D,), sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-12)
+            q, k, v = (F.linear(h, sd[p + f"self_attn.linear_{c}.weight"], sd[p + f"self_attn.linear_{c}.bias"]).view(n, L, H, D // H).transpose(1, 2)
+                       for c in "qkv")
+            a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask).transpose(1, 2).reshape(n, L, D)
+            x = x + F.linear(a, sd[p + "self_attn.linear_out.weight"], sd[p + "self_attn.linear_out.bias"])
+            h = F.layer_norm(x, (D,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-12)
+            h = torch.relu(F.linear(h, sd[p + "feed_forward.w_1.weight"], sd[p + "feed_forward.w_1.bias"]))
+            x = x + F.linear(h, sd[p + "feed_forward.w_2.weight"], sd[p + "feed_forward.w_2.bias"])
+        y = F.layer_norm(x[:, -1], (D,), sd["encoder.after_norm.weight"], sd["encoder.after_norm.bias"], 1e-12)
+        return torch.log_softmax(F.linear(y, sd["decoder.weight"], sd["decoder.bias"]), -1), None
+
+
+def main_lm(args):
+    import statistics
+
+    import lightning
+    from synth import synth_batch, synth_state_dict
+
+    from auto_avsr_amd import decoding
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+    from auto_avsr_amd.lm import TransformerLM
+
+    dev = torch.device("cuda:0")
+    m = E2E(5049, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    lm = TransformerLM(5049, embed_unit=128, att_unit=512, head=8, unit=2048, layer=16)
+    lm.load_state_dict(synth_state_dict(lm.state_dict(), 4))
+    lm = lm.to(dev)
+    toks = [str(i) for i in range(5049)]
+    w_lm = 0.3
+
+    def make(side):
+        bs = lightning.get_beam_search_decoder(m, toks, rnnlm=lm, lm_weight=w_lm, beam_size=args.beam)
+        if side == "foreign":  # the same weights behind a scorer the library does not know
+            bs.scorers["lm"] = bs.full_scorers["lm"] = PlainTorchLM(lm)
+        return bs
+
+    sides = {"native": ("native step (avsr_beam_step with the LM attached)", True),
+             "python": ("python-issued step, cached TransformerLM", False),
+             "foreign": ("python-issued step, plain-torch LM as a foreign scorer (no cache): the build without the lm slot", False)}
+    searches = {k: make(k) for k in sides}
+    rows = []
+    for mode in ("precise", "bf16"):
+        AF.set_mode(mode)
+        AF.invalidate_weight_cache()
+        for T in (100, 400):
+            x, _, _ = synth_batch("video", 1, T, 3, 5049, seed=T, lengths=[T])
+            with torch.no_grad():
+                enc = m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float()
+            times, out = {k: [] for k in sides}, {}
+            for rep in range(args.reps + 1):  # first repetition = warm-up; the sides alternate within a repetition
+                for k, (_, native) in sides.items():
+                    decoding.NATIVE_BEAM = native
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    with torch.no_grad():
+                        nbest = searches[k](enc)
+                    torch.cuda.synchronize()
+                    if rep:
+                        times[k].append((time.perf_counter() - t0) * 1e3)
+                    out[k] = nbest
+                    assert bool(searches[k]._native) == native
+            for k, (label, _) in sides.items():
+                steps = max(len(h.asdict()["yseq"]) for h in out[k]) - 1
+                med = statistics.median(times[k])
+                rows.append({"mode": mode, "step": label, "side": k, "T_frames": T, "beam": args.beam, "lm": "16 x 512, 8 heads, FF 2048, E 128",
+                             "lm_weight": w_lm, "beam_search_ms_median": round(med, 2), "beam_search_ms_min": round(min(times[k]), 2),
+                             "beam_search_ms_max": round(max(times[k]), 2), "repetitions": len(times[k]), "longest_hypothesis_tokens": steps,
+                             "ms_per_token": round(med / max(steps, 1), 3),
+                             "same_best_hypothesis_as_native": out[k][0].asdict()["yseq"] == out["native"][0].asdict()["yseq"]})
+                print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+            base = next(r for r in rows[-3:] if r["side"] == "foreign")["ms_per_token"]
+            for r in rows[-3:]:
+                r["speedup_over_foreign_scorer"] = round(base / r["ms_per_token"], 2)
+    # several utterances in flight with an LM: forward_many at 4 workers
+    AF.set_mode("mixed")
+    AF.invalidate_weight_cache()
+    decoding.NATIVE_BEAM = True
+    encs = []
+    with torch.no_grad():
+        for i in range(args.many):
+            x, _, _ = synth_batch("video", 1, 100, 3, 5049, seed=1000 + i, lengths=[100])
+            encs.append(m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float())
+    ref = None
+    t_many = {"native": []}
+    for rep in range(args.reps + 1):
+        for k in t_many:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = searches[k].forward_many(encs, workers=4)
+            torch.cuda.synchronize()
+            if rep:
+                t_many[k].append((time.perf_counter() - t0) * 1e3)
+            ys = [r[0].asdict()["yseq"] for r in res]
+            ref = ys if ref is None else ref
+            assert ys == ref
+    for k, ts in t_many.items():
+        rows.append({"mode": "mixed", "step": sides[k][0] + ", 4 searches in flight (forward_many)", "side": k, "T_frames": 100, "beam": args.beam,
+                     "utterances": args.many, "beam_search_ms_total_median": round(statistics.median(ts), 1),
+                     "beam_search_ms_total_min": round(min(ts), 1), "beam_search_ms_total_max": round(max(ts), 1),
+                     "utterances_per_sec_search_only": round(args.many / (statistics.median(ts) / 1e3), 2)})
+        print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    AF.set_mode("bf16")
+    print(json.dumps({"metric": "beam search with Transformer-LM shallow fusion, video E2E 250M decoder + 16 x 512 LM, beam search only (encoder output ready)",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
 
 

@@ -1,5 +1,6 @@
 """One beam search (video E2E 250M, synthetic weights, beam 40) for `rocprofv3 --kernel-trace`: the encoder runs in the bf16
-mode so that every split-plane GEMM launch in the trace belongs to the decoding steps.  python tools/prof_decode.py [T] [native]"""
+mode so that every split-plane GEMM launch in the trace belongs to the decoding steps.  python tools/prof_decode.py [T] [native] [lm]
+(lm = 1: shallow fusion with the 16 x 512 Transformer LM of tools/bench_decode.py --lm, weight 0.3)"""
 import os
 import sys
 import time
@@ -13,6 +14,7 @@ import torch  # noqa: E402
 def main():
     T = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     native = (sys.argv[2] if len(sys.argv) > 2 else "1") != "0"
+    with_lm = (sys.argv[3] if len(sys.argv) > 3 else "0") != "0"
     import lightning
     from synth import synth_batch, synth_state_dict
 
@@ -28,7 +30,14 @@ def main():
     m = E2E(5049, "video")
     m.load_state_dict(synth_state_dict(m.state_dict(), 3))
     m = m.to(dev).eval()
-    bs = lightning.get_beam_search_decoder(m, [str(i) for i in range(5049)], beam_size=40)
+    lm = None
+    if with_lm:
+        from auto_avsr_amd.lm import TransformerLM
+
+        lm = TransformerLM(5049)
+        lm.load_state_dict(synth_state_dict(lm.state_dict(), 4))
+        lm = lm.to(dev)
+    bs = lightning.get_beam_search_decoder(m, [str(i) for i in range(5049)], beam_size=40, rnnlm=lm, lm_weight=0.3 if with_lm else 0.0)
     AF.set_mode("bf16")
     x, _, _ = synth_batch("video", 1, T, 3, 5049, seed=T, lengths=[T])
     with torch.no_grad():
