@@ -1,0 +1,567 @@
+// ctc_beam.hip -- the first pass of two-pass decoding: a time-synchronous CTC prefix beam search over a batch of utterances, and
+// the exact CTC log-likelihood of its n-best (the CTC term of the rescoring objective).  Neither is in the reference.
+//
+//   avsr_ctc_beam_search   two launches.  (1) ctc_topk_kernel, one block per (utterance, frame): the K non-blank tokens of
+//       largest log-posterior, sorted, with their values and the blank's -- embarrassingly parallel, off the chain.  (2)
+//       ctc_beam_kernel, ONE workgroup per utterance (grid = B) that walks all of its frames: the beam (<= 64 entries, double
+//       buffered) and the <= W (K + 1) <= 2112 candidates of a frame live in LDS; the (token, lp) rows of the next CB_FCH
+//       frames are already in registers while a chunk is processed.  A frame is four barriers (which order LDS only):
+//         P1  pairs (i, j) / (i, k) of beam entries and tokens: which entry j is the parent prefix of entry i, which token slot
+//             holds i's last token, and which extension (j, k) therefore IS entry i (its mass goes to i, the extension dies);
+//         P2  one thread per candidate: entry i staying (blank, repeated last token, merged extension of its parent) or entry i
+//             extended by token k;
+//         P3  rank of every live candidate among all of them (value descending, index ascending; the N^2 compares are spread over
+//             every thread of the block, partial counts meet in LDS): rank r < W is slot r of the next beam, which is
+//             therefore always sorted -- no selection network;
+//         P4  the W winners write the next beam and its record.
+//       Prefix identity is a pair of 32-bit integers, the two halves of a 64-bit hash chained over the tokens (h' = mix(h, c)),
+//       so "the same prefix" is one integer compare wherever the two copies come from; an entry also carries its parent's
+//       hash and its length.  (Two different prefixes of one utterance would have to collide in 64 bits to be confused:
+//       < 1e-11 per utterance at T = 400, W = 64.)  Every prefix that enters the beam as an extension gets a node id and a
+//       (parent node, token) record in the workspace; with the per-frame beam records (node, length, pb, pnb) and the token
+//       sets these are the history from which the host can replay every frame -- all of it plain stores that nothing waits for.
+//       The n-best token sequences are read back from the node records at the end (len(prefix) steps per hypothesis).
+//   avsr_ctc_score   N label sequences per utterance against one [T][V] matrix of log-posteriors: label builder of ctc_common.h
+//       per sequence, a gather of the 2L+1 extended-label columns, and the alpha recursion of the loss (one wave per sequence).
+#include "prims.h"
+#include "avsr_hip.h"
+#include "ctc_common.h"
+
+namespace {
+
+constexpr int CB_MAXW = 64, CB_MAXK = 32;
+constexpr int CB_MAXC = CB_MAXW * (CB_MAXK + 1);  // candidates of a frame
+constexpr int CB_FCH = 8;                         // frames per staged chunk of (token, lp) rows
+constexpr int CB_STG = 3;                         // registers per thread that hold the next chunk: 8 * 65 words <= 3 * 256
+constexpr int CB_NT_MIN = 256, CB_NT_MAX = 1024;  // threads of the search's block
+constexpr int TK_NT = 256;
+
+AVSR_DEV float neg_inf() { return -INFINITY; }
+// log(e^a + e^b) with -inf as the empty sum; expf / logf of normal accuracy (the frame-by-frame tests assume it)
+AVSR_DEV float lse2(float a, float b) {
+    const float m = fmaxf(a, b);
+    if (m == neg_inf()) return m;
+    return m + logf(1.0f + expf(-fabsf(a - b)));
+}
+// Barrier between the phases of a frame: orders LDS only.  __syncthreads() would also wait for every global store in flight -- the
+// search's history, which nothing in the frame loop reads back -- and put a memory round trip on every frame of the chain.
+AVSR_DEV void lds_barrier() {
+#ifdef AVSR_EMU
+    emu::sync_threads();
+#else
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+#endif
+}
+AVSR_DEV unsigned cb_f2key(float f) {  // order-preserving integer image of a float; > 0 for every non-NaN value
+    const unsigned u = __builtin_bit_cast(unsigned, f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+AVSR_DEV uint64_t cb_hash(uint64_t h, int c) {  // splitmix64 finalizer over (hash of the prefix, next token)
+    uint64_t z = h + ((uint64_t)(unsigned)(c + 1)) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+constexpr uint64_t CB_ROOT_HASH = 0x243F6A8885A308D3ull, CB_NO_PARENT = 0ull;
+
+// ---- per (utterance, frame): the K largest non-blank log-posteriors, by decreasing value (ties: the smaller token id first)
+__global__ __launch_bounds__(TK_NT) void ctc_topk_kernel(const float* __restrict__ lp, long ld, const int64_t* __restrict__ in_lens,
+                                                         int blank, int K, int Tlen, int V, int32_t* __restrict__ tok,
+                                                         float* __restrict__ val, float* __restrict__ blk) {
+    AVSR_DYN_SMEM(smem);
+    unsigned* keys = reinterpret_cast<unsigned*>(smem);  // [V]; a thread only ever touches the elements tid, tid + TK_NT, ...
+    __shared__ unsigned red[2][TK_NT / 64][2];
+    const long row = blockIdx.x;
+    const int b = (int)(row / Tlen), t = (int)(row % Tlen), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if ((int64_t)t >= in_lens[b]) return;  // (block-uniform) frames beyond the utterance are not read
+    const float* x = lp + row * ld;
+    unsigned bk = 0u, bi = 0u;  // this thread's best remaining (key, ~index); key 0 = nothing left
+    auto rescan = [&]() {
+        bk = 0u;
+        bi = 0u;
+        for (int i = tid; i < V; i += TK_NT) {
+            const unsigned k = keys[i];
+            if (k > bk) {  // (ascending i: the first of equal keys stays)
+                bk = k;
+                bi = ~(unsigned)i;
+            }
+        }
+    };
+    for (int i = tid; i < V; i += TK_NT) keys[i] = i == blank ? 0u : cb_f2key(x[i]);
+    if (tid == 0) blk[row] = x[blank];
+    rescan();
+    for (int k = 0; k < K; k++) {
+        unsigned mk = bk, mi = bi;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const unsigned ok = (unsigned)__shfl_xor((int)mk, m), oi = (unsigned)__shfl_xor((int)mi, m);
+            if (ok > mk || (ok == mk && oi > mi)) {
+                mk = ok;
+                mi = oi;
+            }
+        }
+        if (lane == 0) {
+            red[k & 1][wave][0] = mk;
+            red[k & 1][wave][1] = mi;
+        }
+        __syncthreads();
+        mk = red[k & 1][0][0];
+        mi = red[k & 1][0][1];
+#pragma unroll
+        for (int w = 1; w < TK_NT / 64; w++) {
+            const unsigned ok = red[k & 1][w][0], oi = red[k & 1][w][1];
+            if (ok > mk || (ok == mk && oi > mi)) {
+                mk = ok;
+                mi = oi;
+            }
+        }
+        const int idx = (int)~mi;  // (K <= V - 1: a key is always left)
+        if (tid == 0) {
+            tok[row * K + k] = idx;
+            val[row * K + k] = x[idx];
+        }
+        if (idx % TK_NT == tid) {
+            keys[idx] = 0u;
+            rescan();
+        }
+    }
+}
+
+struct BeamArgs {
+    const int32_t* tok;  // [B][T][K]
+    const float* val;    // [B][T][K]
+    const float* blk;    // [B][T]
+    int32_t* cnt;        // [B][T]
+    int32_t* node;       // [B][T*W+1][2]
+    int32_t* beam;       // [B][T][W][4]
+    const int64_t* in_lens;
+    int32_t *tokens, *lens, *n_valid;
+    float *score, *pb, *pnb;
+    int W, K, nbest, T;
+};
+
+// ---- one workgroup per utterance walks its frames
+__global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
+    // the beam, double buffered: hash of the prefix and of its parent prefix, last token, length, node id, pb, pnb, total
+    __shared__ uint64_t s_h[2][CB_MAXW], s_hp[2][CB_MAXW];
+    __shared__ int s_last[2][CB_MAXW], s_len[2][CB_MAXW], s_node[2][CB_MAXW];
+    __shared__ float s_pb[2][CB_MAXW], s_pnb[2][CB_MAXW], s_tot[2][CB_MAXW];
+    __shared__ int s_n[2];
+    __shared__ int s_par[CB_MAXW], s_kpos[CB_MAXW];  // of the current beam: slot of the parent prefix / token slot of the last token, -1: none
+    __shared__ int s_kill[CB_MAXW * CB_MAXK];        // extension (j, k) was merged into a staying entry at frame (value - 1)
+    __shared__ __attribute__((aligned(16))) float s_cv[CB_MAXC + 4];  // candidate totals
+    __shared__ float s_cpnb[CB_MAXC], s_cpb[CB_MAXW];
+    __shared__ int s_rank[CB_MAXC];  // candidates that beat candidate s, summed over the parts of the block
+    __shared__ int s_live;           // candidates of the frame that carry mass
+    __shared__ int s_stage[2][CB_FCH * (2 * CB_MAXK + 1)];  // per frame of a chunk: K tokens, K values, the blank's value
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+    const int W = a.W, K = a.K, T = a.T, K1 = K + 1, RW = 2 * K + 1;
+    // P3: the block is `parts` groups of Cw threads (whole waves); group g compares every candidate with its share of the others
+    const int Cw = (W * K1 + 63) / 64 * 64, parts = Cw <= NT ? NT / Cw : 1;
+    const int part = parts > 1 ? tid / Cw : 0, s_first = parts > 1 ? tid - part * Cw : tid, s_step = parts > 1 ? Cw : NT;
+    int Tb = (int)(a.in_lens[b] < (int64_t)T ? a.in_lens[b] : (int64_t)T);
+    if (Tb < 0) Tb = 0;
+    const int32_t* g_tok = a.tok + (long)b * T * K;
+    const float* g_val = a.val + (long)b * T * K;
+    const float* g_blk = a.blk + (long)b * T;
+    int32_t* g_cnt = a.cnt + (long)b * T;
+    int32_t* g_node = a.node + (long)b * ((long)T * W + 1) * 2;
+    int32_t* g_beam = a.beam + (long)b * T * W * 4;
+
+    if (tid == 0) {
+        s_h[0][0] = CB_ROOT_HASH;
+        s_hp[0][0] = CB_NO_PARENT;
+        s_last[0][0] = -1;
+        s_len[0][0] = 0;
+        s_node[0][0] = 0;
+        s_pb[0][0] = 0.f;
+        s_pnb[0][0] = neg_inf();
+        s_tot[0][0] = 0.f;
+        s_n[0] = 1;
+        s_par[0] = -1;
+        s_kpos[0] = -1;
+        g_node[0] = -1;
+        g_node[1] = -1;
+    }
+    for (int i = tid; i < CB_MAXW * CB_MAXK; i += NT) s_kill[i] = 0;
+
+    // staging of the token rows: chunk c = frames [c * FCH, (c + 1) * FCH), word w = f * RW + x of a chunk
+    int pre[CB_STG];
+    auto fetch = [&](int chunk) {
+#pragma unroll
+        for (int q = 0; q < CB_STG; q++) {
+            const int w = tid + q * NT, f = w / RW, x = w - f * RW, t = chunk * CB_FCH + f;
+            int v = 0;
+            if (f < CB_FCH && t < Tb) {
+                if (x < K) v = g_tok[(long)t * K + x];
+                else if (x < 2 * K) v = __builtin_bit_cast(int, g_val[(long)t * K + x - K]);
+                else v = __builtin_bit_cast(int, g_blk[t]);
+            }
+            pre[q] = v;
+        }
+    };
+    auto stash = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < CB_STG; q++) {
+            const int w = tid + q * NT;
+            if (w < CB_FCH * RW) s_stage[buf][w] = pre[q];
+        }
+    };
+    fetch(0);
+    stash(0);
+    fetch(1);
+    __syncthreads();
+
+    int cur = 0;
+    for (int t = 0; t < Tb; t++) {
+        const int chunk = t / CB_FCH, f = t - chunk * CB_FCH;
+        const int* st_tok = &s_stage[chunk & 1][f * RW];
+        const float* st_val = reinterpret_cast<const float*>(st_tok + K);
+        const float lpb = st_val[K];
+        const int n = s_n[cur], nxt = cur ^ 1, N = n * K1, stamp = t + 1;
+        // ---- P1: parent slots, token slots of the last tokens, merged extensions
+        for (int p = tid; p < n * n; p += NT) {
+            const int i = p / n, j = p - i * n;
+            if (s_hp[cur][i] == s_h[cur][j] && s_len[cur][i] == s_len[cur][j] + 1) {
+                s_par[i] = j;
+                const int c = s_last[cur][i];
+                for (int k = 0; k < K; k++)
+                    if (st_tok[k] == c) s_kill[j * K + k] = stamp;
+            }
+        }
+        for (int p = tid; p < n * K; p += NT) {
+            const int i = p / K, k = p - i * K;
+            if (st_tok[k] == s_last[cur][i]) s_kpos[i] = k;
+        }
+        if (tid == 0) {
+            s_n[nxt] = 0;
+            s_live = 0;
+        }
+        lds_barrier();
+        // ---- P2: the candidates.  Slot i * (K + 1) + k: entry i extended by token k (k < K) or staying (k == K)
+        int alive = 0;
+        for (int s = tid; s < N; s += NT) {
+            const int i = s / K1, k = s - i * K1;
+            float v;
+            if (k == K) {
+                const float pbn = s_tot[cur][i] + lpb;
+                const int kp = s_kpos[i], j = s_par[i];
+                float pnbn = neg_inf();
+                if (kp >= 0) {
+                    const float lpc = st_val[kp];
+                    pnbn = s_pnb[cur][i] + lpc;
+                    if (j >= 0) pnbn = lse2(pnbn, (s_last[cur][j] != s_last[cur][i] ? s_tot[cur][j] : s_pb[cur][j]) + lpc);
+                }
+                s_cpb[i] = pbn;
+                s_cpnb[s] = pnbn;
+                v = lse2(pbn, pnbn);
+            } else {
+                v = (st_tok[k] != s_last[cur][i] ? s_tot[cur][i] : s_pb[cur][i]) + st_val[k];
+                if (s_kill[i * K + k] == stamp) v = neg_inf();
+                s_cpnb[s] = v;
+            }
+            s_cv[s] = v;
+            s_rank[s] = 0;
+            alive += v > neg_inf();
+        }
+        alive = (int)wave_sum((float)alive);
+        if ((tid & 63) == 0 && alive) atomicAdd(&s_live, alive);
+        if (tid < 4) s_cv[N + tid] = neg_inf();  // (the rank loop reads whole groups of 4)
+        lds_barrier();
+        // ---- P3: rank r < W = slot r of the next beam.  Part g of the block counts, for every candidate, those of ITS quarter (or
+        // so) of the candidates that beat it; the counts meet in LDS
+        if (part < parts) {
+            const int groups = (N + 3) / 4, per = (groups + parts - 1) / parts;
+            const int u0 = 4 * part * per, u1 = min(4 * groups, u0 + 4 * per);
+            for (int s = s_first; s < N; s += s_step) {
+                const float v = s_cv[s];
+                if (!(v > neg_inf())) continue;
+                // the 64 candidates of a wave are consecutive: groups of 4 wholly below all of them beat one on a tie, groups wholly
+                // above never do, and only the <= 17 groups in between need the index compare
+                const int s_lo = s - (tid & 63);
+                const int ua = max(u0, min(u1, s_lo / 4 * 4)), uc = min(u1, max(ua, (s_lo + 63) / 4 * 4 + 4));
+                int rank = 0;
+#pragma unroll 4
+                for (int u = u0; u < ua; u += 4) {
+                    const f32x4 q = *reinterpret_cast<const f32x4*>(&s_cv[u]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) rank += q[e] >= v;
+                }
+                for (int u = ua; u < uc; u += 4) {
+                    const f32x4 q = *reinterpret_cast<const f32x4*>(&s_cv[u]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) rank += (q[e] > v) | ((q[e] == v) & (u + e < s));
+                }
+#pragma unroll 4
+                for (int u = uc; u < u1; u += 4) {
+                    const f32x4 q = *reinterpret_cast<const f32x4*>(&s_cv[u]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) rank += q[e] > v;
+                }
+                if (rank) atomicAdd(&s_rank[s], rank);
+            }
+        }
+        lds_barrier();
+        for (int s = tid; s < N; s += NT) {
+            const float v = s_cv[s];
+            if (!(v > neg_inf())) continue;
+            const int rank = s_rank[s], live = s_live;
+            if (rank >= W) continue;
+            const int i = s / K1, k = s - i * K1, r = rank;
+            int node = s_node[cur][i], len = s_len[cur][i];
+            float pbn = neg_inf();
+            if (k == K) {
+                s_h[nxt][r] = s_h[cur][i];
+                s_hp[nxt][r] = s_hp[cur][i];
+                s_last[nxt][r] = s_last[cur][i];
+                pbn = s_cpb[i];
+            } else {
+                const int c = st_tok[k];
+                s_h[nxt][r] = cb_hash(s_h[cur][i], c);
+                s_hp[nxt][r] = s_h[cur][i];
+                s_last[nxt][r] = c;
+                const int parent = node;
+                node = 1 + t * W + r;
+                len += 1;
+                g_node[2 * (long)node] = parent;
+                g_node[2 * (long)node + 1] = c;
+            }
+            const float pnbn = s_cpnb[s];
+            s_len[nxt][r] = len;
+            s_node[nxt][r] = node;
+            s_pb[nxt][r] = pbn;
+            s_pnb[nxt][r] = pnbn;
+            s_tot[nxt][r] = v;
+            i32x4 rec;
+            rec[0] = node;
+            rec[1] = len;
+            rec[2] = __builtin_bit_cast(int, pbn);
+            rec[3] = __builtin_bit_cast(int, pnbn);
+            *reinterpret_cast<i32x4*>(&g_beam[((long)t * W + r) * 4]) = rec;
+            const int n_new = live < W ? live : W;
+            if (r == n_new - 1) {
+                s_n[nxt] = n_new;
+                g_cnt[t] = n_new;
+            }
+        }
+        for (int i = tid; i < W; i += NT) {  // (slots of the next beam; P1 of the next frame fills them in)
+            s_par[i] = -1;
+            s_kpos[i] = -1;
+        }
+        if (f == CB_FCH - 1) {  // the next chunk's rows go from the registers to the other stage buffer; the one after is requested
+            stash((chunk + 1) & 1);
+            fetch(chunk + 2);
+        }
+        lds_barrier();
+        if (tid == 0 && s_n[nxt] == 0) g_cnt[t] = 0;  // (every candidate -inf: the search of this utterance is over)
+        cur = nxt;
+    }
+
+    // ---- the n-best: the beam is sorted; token sequences come back from the node records
+#ifndef AVSR_EMU
+    __threadfence();
+#endif
+    __syncthreads();
+    const int n = s_n[cur], nbest = a.nbest;
+    const int nv = n < nbest ? n : nbest;
+    if (tid == 0) a.n_valid[b] = nv;
+    int32_t* out = a.tokens + (long)b * nbest * T;
+    for (int r = 0; r < nbest; r++) {
+        const int len = r < nv ? s_len[cur][r] : 0;
+        for (int i = len + tid; i < T; i += NT) out[(long)r * T + i] = -1;
+    }
+    if (tid < nbest) {
+        const int r = tid;
+        const bool ok = r < nv;
+        a.lens[(long)b * nbest + r] = ok ? s_len[cur][r] : 0;
+        a.score[(long)b * nbest + r] = ok ? s_tot[cur][r] : neg_inf();
+        a.pb[(long)b * nbest + r] = ok ? s_pb[cur][r] : neg_inf();
+        a.pnb[(long)b * nbest + r] = ok ? s_pnb[cur][r] : neg_inf();
+        if (ok) {
+            int node = s_node[cur][r];
+            for (int i = s_len[cur][r] - 1; i >= 0 && node > 0; i--) {
+                out[(long)r * T + i] = g_node[2 * (long)node + 1];
+                node = g_node[2 * (long)node];
+            }
+        }
+    }
+}
+
+// ---- avsr_ctc_score: lpg[q, t, s] = lp[q / N, t, ext[q, s]] for the sequences q = b * N + i
+__global__ __launch_bounds__(256) void ctc_score_gather_kernel(const float* __restrict__ lp, long ld, const int* __restrict__ ext,
+                                                               const int* __restrict__ lens, const int64_t* __restrict__ in_lens,
+                                                               float* __restrict__ lpg, int N, int Tlen, int Smax) {
+    const long qt = blockIdx.x;
+    const int q = (int)(qt / Tlen), t = (int)(qt % Tlen), b = q / N;
+    if ((int64_t)t >= in_lens[b]) return;
+    const int S = 2 * lens[q] + 1;
+    const float* x = lp + ((long)b * Tlen + t) * ld;
+    for (int s = threadIdx.x; s < S; s += 256) lpg[qt * Smax + s] = x[ext[(long)q * Smax + s]];
+}
+
+AVSR_DEV float score_add3(float a, float b, float c) {
+    const float m = fmaxf(a, fmaxf(b, c));
+    if (m <= LOG_ZERO) return LOG_ZERO;
+    return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
+}
+
+// the alpha recursion of loss.hip (one wave per sequence, SPL contiguous states per lane, CTC_PF frames of emissions in flight),
+// forward only and without the stored trellis
+template <int SPL>
+__global__ __launch_bounds__(64) void ctc_score_alpha_kernel(const float* __restrict__ lpg, const int* __restrict__ ext,
+                                                             const int* __restrict__ lens, const int64_t* __restrict__ in_lens,
+                                                             float* __restrict__ loglik, int N, int Tlen, int Smax) {
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int L = lens[q], S = 2 * L + 1;
+    int Tb = (int)(in_lens[q / N] < (int64_t)Tlen ? in_lens[q / N] : (int64_t)Tlen);
+    const int* e = ext + (long)q * Smax;
+    const float* lp = lpg + (long)q * Tlen * Smax;
+    const int blank = e[0], s0 = lane * SPL;
+    if (Tb <= 0) {
+        if (lane == 0) loglik[q] = L == 0 ? 0.f : -INFINITY;
+        return;
+    }
+    bool skip[SPL], valid[SPL];
+    float cur[SPL];
+#pragma unroll
+    for (int i = 0; i < SPL; i++) {
+        const int s = s0 + i;
+        valid[i] = s < S;
+        skip[i] = valid[i] && (s >= 2) && (e[s] != blank) && (e[s] != e[s - 2]);
+        cur[i] = (valid[i] && s < 2) ? lp[s] : LOG_ZERO;
+    }
+    float pre[CTC_PF][SPL];
+    auto fetch = [&](int t, float (&dst)[SPL]) {
+#pragma unroll
+        for (int i = 0; i < SPL; i++) dst[i] = (t < Tb && valid[i]) ? lp[(long)t * Smax + s0 + i] : 0.f;
+    };
+#pragma unroll
+    for (int j = 0; j < CTC_PF; j++) fetch(1 + j, pre[j]);
+    for (int t0 = 1; t0 < Tb; t0 += CTC_PF) {
+#pragma unroll
+        for (int j = 0; j < CTC_PF; j++) {
+            const int t = t0 + j;
+            if (t >= Tb) break;
+            const float n1 = wave_up1(cur[SPL - 1], LOG_ZERO);
+            const float n2 = SPL >= 2 ? wave_up1(cur[SPL >= 2 ? SPL - 2 : 0], LOG_ZERO) : wave_up1(n1, LOG_ZERO);
+            float nxt[SPL];
+#pragma unroll
+            for (int i = 0; i < SPL; i++) {
+                const float a1 = i >= 1 ? cur[i >= 1 ? i - 1 : 0] : n1;
+                const float a2 = i >= 2 ? cur[i >= 2 ? i - 2 : 0] : (i == 1 ? n1 : n2);
+                const float v = score_add3(cur[i], a1, skip[i] ? a2 : LOG_ZERO) + pre[j][i];
+                nxt[i] = (valid[i] && v > LOG_ZERO) ? v : LOG_ZERO;
+            }
+#pragma unroll
+            for (int i = 0; i < SPL; i++) cur[i] = nxt[i];
+            fetch(t + CTC_PF, pre[j]);
+        }
+    }
+    float m1 = LOG_ZERO, m2 = LOG_ZERO;  // alpha(S - 1), alpha(S - 2)
+#pragma unroll
+    for (int i = 0; i < SPL; i++) {
+        const int s = s0 + i;
+        if (valid[i] && s == S - 1) m1 = cur[i];
+        if (valid[i] && s == S - 2) m2 = cur[i];
+    }
+    m1 = wave_max(m1);
+    m2 = wave_max(m2);
+    const float tot = score_add3(m1, m2, LOG_ZERO);
+    if (lane == 0) loglik[q] = tot <= LOG_ZERO * 0.5f ? -INFINITY : tot;
+}
+
+int64_t align16(int64_t x) { return (x + 15) / 16 * 16; }
+
+}  // namespace
+
+// Workspace layout (header): tok | val | blk | cnt | node | (to 16 bytes) beam
+static int64_t beam_rec_offset(int B, int T, int W, int K) {
+    const int64_t words = (int64_t)B * T * K * 2 + (int64_t)B * T * 2 + (int64_t)B * ((int64_t)T * W + 1) * 2;
+    return align16(words * 4);
+}
+
+extern "C" int64_t avsr_ctc_beam_workspace_bytes(int B, int T, int W, int K) {
+    if (B <= 0 || T <= 0 || W <= 0 || K <= 0) return 16;
+    return beam_rec_offset(B, T, W, K) + (int64_t)B * T * W * 16;
+}
+
+extern "C" int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
+                                    int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid,
+                                    void* workspace, int B, int T, int V, hipStream_t stream) {
+    AVSR_REQUIRE(W >= 2 && W <= CB_MAXW, "ctc_beam_search: beam must be 2 .. 64");
+    AVSR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V - 1, "ctc_beam_search: token budget must be 1 .. min(32, V - 1)");
+    AVSR_REQUIRE(nbest >= 1 && nbest <= W, "ctc_beam_search: nbest must be 1 .. beam");
+    AVSR_REQUIRE(blank >= 0 && blank < V && V <= ld, "ctc_beam_search: blank id outside the vocabulary");
+    AVSR_REQUIRE(V <= 16000, "ctc_beam_search: at most 16000 tokens (the row's keys live in LDS)");
+    AVSR_REQUIRE(T >= 1 && (int64_t)T * W < (1 << 30), "ctc_beam_search: 1 .. 2^30 / beam frames");
+    AVSR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_beam_search: workspace must be 16-byte aligned");
+    if (B <= 0) return 0;
+    BeamArgs a;
+    int32_t* tok = reinterpret_cast<int32_t*>(workspace);
+    float* val = reinterpret_cast<float*>(tok + (int64_t)B * T * K);
+    float* blk = val + (int64_t)B * T * K;
+    a.tok = tok;
+    a.val = val;
+    a.blk = blk;
+    a.cnt = reinterpret_cast<int32_t*>(blk + (int64_t)B * T);
+    a.node = a.cnt + (int64_t)B * T;
+    a.beam = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + beam_rec_offset(B, T, W, K));
+    a.in_lens = in_lens;
+    a.tokens = tokens;
+    a.lens = lens;
+    a.n_valid = n_valid;
+    a.score = score;
+    a.pb = pb;
+    a.pnb = pnb;
+    a.W = W;
+    a.K = K;
+    a.nbest = nbest;
+    a.T = T;
+    AVSR_LAUNCH(ctc_topk_kernel, dim3((unsigned)((int64_t)B * T)), dim3(TK_NT), (size_t)V * sizeof(unsigned), stream, lp, (long)ld,
+                in_lens, blank, K, T, V, tok, val, blk);
+    // four threads per candidate where a block can hold them (the rank loop of P3 is the longest stretch of a frame), whole waves
+    int nt = (W * (K + 1) + 63) / 64 * 64 * 4;
+    nt = nt < CB_NT_MIN ? CB_NT_MIN : (nt > CB_NT_MAX ? CB_NT_MAX : nt);
+    AVSR_LAUNCH(ctc_beam_kernel, dim3(B), dim3(nt), 0, stream, a);
+    AVSR_CHECK_LAUNCH("ctc_beam_search");
+    return 0;
+}
+
+// Workspace layout: lpg[B*N*T*Smax] f32 | ext[B*N*Smax] i32 | lens[B*N] i32
+extern "C" int64_t avsr_ctc_score_workspace_bytes(int B, int N, int T, int Lmax) {
+    if (B <= 0 || N <= 0 || T <= 0 || Lmax < 0) return 16;
+    const int64_t Smax = 2 * (int64_t)Lmax + 1, Q = (int64_t)B * N;
+    return align16((Q * T * Smax + Q * Smax + Q) * 4);
+}
+
+extern "C" int avsr_ctc_score(const float* lp, int64_t ld, const int64_t* labels, int N, int Lmax, int ignore_id,
+                              const int64_t* in_lens, int blank, float* loglik, void* workspace, int B, int T, int V,
+                              hipStream_t stream) {
+    AVSR_REQUIRE(Lmax >= 0 && Lmax <= 255, "ctc_score: at most 255 labels per sequence");
+    AVSR_REQUIRE(blank >= 0 && blank < V && V <= ld, "ctc_score: blank id outside the vocabulary");
+    AVSR_REQUIRE(ignore_id < 0 || ignore_id >= V, "ctc_score: ignore_id must not be a token id");
+    AVSR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "ctc_score: workspace must be 4-byte aligned");
+    AVSR_REQUIRE(T >= 0 && (int64_t)B * N * (T > 0 ? T : 1) < (1ll << 31), "ctc_score: too many (sequence, frame) pairs");
+    if (B <= 0 || N <= 0) return 0;
+    const int Smax = 2 * Lmax + 1, Q = B * N;
+    float* lpg = reinterpret_cast<float*>(workspace);
+    int* ext = reinterpret_cast<int*>(lpg + (int64_t)Q * T * Smax);
+    int* lens = ext + (int64_t)Q * Smax;
+    AVSR_LAUNCH(ctc_prepare_kernel, dim3(Q), dim3(64), 0, stream, labels, Lmax, ignore_id, blank, ext, Smax, lens);
+    if (T > 0)
+        AVSR_LAUNCH(ctc_score_gather_kernel, dim3((unsigned)((int64_t)Q * T)), dim3(256), 0, stream, lp, (long)ld, ext, lens, in_lens, lpg, N,
+                    T, Smax);
+    const int spl = (Smax + 63) / 64;
+#define AVSR_CTC_SC(NS) AVSR_LAUNCH(ctc_score_alpha_kernel<NS>, dim3(Q), dim3(64), 0, stream, lpg, ext, lens, in_lens, loglik, N, T, Smax)
+    if (spl <= 1) AVSR_CTC_SC(1);
+    else if (spl == 2) AVSR_CTC_SC(2);
+    else if (spl == 3) AVSR_CTC_SC(3);
+    else if (spl == 4) AVSR_CTC_SC(4);
+    else if (spl <= 6) AVSR_CTC_SC(6);
+    else AVSR_CTC_SC(8);
+#undef AVSR_CTC_SC
+    AVSR_CHECK_LAUNCH("ctc_score");
+    return 0;
+}

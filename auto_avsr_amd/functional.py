@@ -1423,7 +1423,7 @@ from .functional_attention import (  # noqa: E402,F401
     prepare_pos_proj, _placeholders, _placeholder_grad, PosProjFn, _proj, AttentionCoreFn, attention_core,
     MhaSublayerFn, mha_sublayer, MemoryKVFn, memory_kv)
 from .functional_heads import (  # noqa: E402,F401
-    ScaleDropoutFn, scale_dropout, EmbedFn, embed, CtcLossFn, ctc_loss, ctc_align, CeSmoothFn, ce_smooth, AddRowsFn, add,
-    log_softmax)
+    ScaleDropoutFn, scale_dropout, EmbedFn, embed, CtcLossFn, ctc_loss, ctc_align, ctc_beam_search, ctc_score, CeSmoothFn,
+    ce_smooth, AddRowsFn, add, log_softmax)
 from .functional_frontend import (  # noqa: E402,F401
     _bn_fwd_params, _bn_bwd, bn_tuple, BasicBlockFn, basic_block, StemFn, stem, AvgPoolFn, avg_pool)

@@ -112,6 +112,39 @@ def ctc_align(logits, labels, in_lens, blank=0, ignore_id=-1):
         return ops.ctc_align(l2, ld, lab, lens, B, Tn, V, blank=int(blank), ignore_id=int(ignore_id))
 
 
+def _lp_rows(lp):
+    """f32 log-posteriors [B,T,V] (possibly a [..., :V] view of a pitch-padded buffer) as the (rows, ld) pair the kernels read."""
+    B, Tn, V = lp.shape
+    pit = _pitched_2d(lp, B * Tn, V) if lp.dtype == torch.float32 else None
+    if pit is None:
+        ld = padded_cols(V)
+        buf = torch.zeros(B * Tn, ld, dtype=torch.float32, device=lp.device)
+        buf[:, :V].copy_(lp.reshape(B * Tn, V))
+        pit = (buf, ld)
+    return pit
+
+
+def ctc_beam_search(lp, in_lens, blank=0, beam=16, topk=16, nbest=None):
+    """CTC prefix beam search over log-posteriors [B,T,V] (csrc/ctc_beam.hip; ops.ctc_beam_search describes the result)."""
+    with torch.no_grad():
+        lp = lp.detach()
+        B, Tn, V = lp.shape
+        l2, ld = _lp_rows(lp)
+        lens = in_lens.to(device=lp.device, dtype=torch.int64).contiguous()
+        return ops.ctc_beam_search(l2, ld, lens, B, Tn, V, blank=int(blank), beam=beam, topk=topk, nbest=nbest)
+
+
+def ctc_score(lp, labels, in_lens, blank=0, ignore_id=-1):
+    """Exact log P_ctc of labels [B,N,L] (padded with ignore_id) against ONE copy of the log-posteriors [B,T,V]: f32 [B,N]."""
+    with torch.no_grad():
+        lp = lp.detach()
+        B, Tn, V = lp.shape
+        l2, ld = _lp_rows(lp)
+        lab = labels.to(device=lp.device, dtype=torch.int64).contiguous()
+        lens = in_lens.to(device=lp.device, dtype=torch.int64).contiguous()
+        return ops.ctc_score(l2, ld, lab, lens, B, Tn, V, blank=int(blank), ignore_id=int(ignore_id))
+
+
 class CeSmoothFn(torch.autograd.Function):
     """label_smoothing_loss.py:41-63 (sum over tokens / B) + nets_utils.py:272-292 accuracy, on f32 logits
     [B,L,V].  Returns (loss, n_hits, n_valid) as device scalars."""

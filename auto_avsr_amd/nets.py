@@ -538,6 +538,13 @@ class CTC(nn.Module):
         logits = self._logits(hs_pad, False)  # (B, T, V)
         return AF.ctc_align(logits, ys_pad, hlens, blank=blank_id, ignore_id=self.ignore_id)
 
+    # ---- first pass of two-pass decoding: time-synchronous prefix beam search on the device (csrc/ctc_beam.hip)
+    def prefix_beam_search(self, hs_pad, hlens, beam=16, topk=16, nbest=None, blank_id=0):
+        """Not in the reference: hidden states (B, T, D), lengths (B,) -> the n-best prefixes of a CTC prefix beam search over the
+        head's log-softmax (beam entries kept per frame, `topk` non-blank tokens considered per frame), as the dict of device
+        tensors of ops.ctc_beam_search: tokens (B, nbest, T) padded with -1, lens, score, pb, pnb (B, nbest), n_valid (B,)."""
+        return AF.ctc_beam_search(self.log_softmax(hs_pad), hlens, blank=blank_id, beam=beam, topk=topk, nbest=nbest)
+
     def forced_align(self, h, y, blank_id=0):
         """ctc.py:95-158: hidden states (T, D) or (1, T, D), id sequence (L,) -> list of T token ids (python ints)."""
         if h.dim() == 2:

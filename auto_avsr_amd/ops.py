@@ -570,6 +570,75 @@ def ctc_align(logits, ld, labels, in_lens, B, T, V, blank=0, ignore_id=-1):
     return ali, score
 
 
+def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=None):
+    """CTC prefix beam search (csrc/ctc_beam.hip).  lp: f32 [B*T, ld] log-posteriors; in_lens int64 [B].  Returns a dict of
+    device tensors: tokens int32 [B, nbest, T] (-1 padded), lens int32 [B, nbest], score / pb / pnb f32 [B, nbest], n_valid int32
+    [B], and the history of the search as views of its workspace (ctc_beam_trace rebuilds the per-frame beams from them):
+    topk_tok int32 / topk_val f32 [B, T, K], blank_val f32 [B, T], count int32 [B, T], node int32 [B, T*W+1, 2] (parent, token),
+    slots int32 [B, T, W, 4] (node id, length, pb bits, pnb bits).  Rows t >= in_lens[b] of the history are not written."""
+    W, K = int(beam), int(topk)
+    nbest = W if nbest is None else int(nbest)
+    dev = lp.device
+    ws_bytes = call("avsr_ctc_beam_workspace_bytes", B, T, W, K)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    n_valid = torch.empty(B, dtype=torch.int32, device=dev)
+    score, pb, pnb = (torch.empty(B, nbest, dtype=torch.float32, device=dev) for _ in range(3))
+    call("avsr_ctc_beam_search", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, _ptr(tokens), _ptr(lens), _ptr(score),
+         _ptr(pb), _ptr(pnb), _ptr(n_valid), _ptr(ws), B, T, V, _stream(lp))
+    out = {"tokens": tokens, "lens": lens, "score": score, "pb": pb, "pnb": pnb, "n_valid": n_valid, "beam": W, "topk": K}
+    if T > 0:
+        o = 0
+        for name, shape, as_f32 in (("topk_tok", (B, T, K), False), ("topk_val", (B, T, K), True), ("blank_val", (B, T), True),
+                                    ("count", (B, T), False), ("node", (B, T * W + 1, 2), False)):
+            n = 1
+            for s in shape:
+                n *= s
+            v = ws[o:o + n].view(shape)
+            out[name] = v.view(torch.float32) if as_f32 else v
+            o += n
+        o = (o * 4 + 15) // 16 * 4
+        out["slots"] = ws[o:o + B * T * W * 4].view(B, T, W, 4)
+    return out
+
+
+def ctc_beam_trace(res, in_lens):
+    """Host view of the history ctc_beam_search leaves: (trace, topk) with trace[b][t] = [(prefix tuple, pb, pnb), ...] in beam
+    order (best first) after frame t and topk[b][t] = the frame's token ids, for t < in_lens[b]."""
+    tok, cnt = res["topk_tok"].cpu(), res["count"].cpu()
+    node, slots = res["node"].cpu(), res["slots"].cpu()
+    vals = slots[..., 2:].contiguous().view(torch.float32)
+    trace, topk = [], []
+    for b, Tb in enumerate(int(t) for t in in_lens):
+        Tb = max(0, min(Tb, tok.shape[1]))
+        prefix = {0: ()}
+        nb, frames = node[b].tolist(), []
+        for t in range(Tb):
+            entries = []
+            for r in range(int(cnt[b, t])):
+                nid = int(slots[b, t, r, 0])
+                if nid not in prefix:
+                    prefix[nid] = prefix[nb[nid][0]] + (nb[nid][1],)
+                entries.append((prefix[nid], float(vals[b, t, r, 0]), float(vals[b, t, r, 1])))
+            frames.append(entries)
+        trace.append(frames)
+        topk.append([tok[b, t].tolist() for t in range(Tb)])
+    return trace, topk
+
+
+def ctc_score(lp, ld, labels, in_lens, B, T, V, blank=0, ignore_id=-1):
+    """Exact CTC log-likelihood of N label sequences per utterance against one copy of its log-posteriors.  lp: f32 [B*T, ld];
+    labels int64 [B, N, Lmax] padded with ignore_id; in_lens int64 [B].  Returns loglik f32 [B, N] (-inf: does not fit)."""
+    _, N, Lmax = labels.shape
+    ws_bytes = call("avsr_ctc_score_workspace_bytes", B, N, T, Lmax)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=lp.device)
+    out = torch.empty(B, N, dtype=torch.float32, device=lp.device)
+    call("avsr_ctc_score", _ptr(lp), ld, _ptr(labels), N, Lmax, int(ignore_id), _ptr(in_lens), int(blank), _ptr(out), _ptr(ws),
+         B, T, V, _stream(lp))
+    return out
+
+
 def ce_smooth(logits, ld, target, V, smoothing, want_grad=True, ignore_id=-1):
     rows = target.numel()
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)

@@ -37,6 +37,11 @@ def parse_args(argv=None):
     p.add_argument("--lm-conf", type=str, default=None,
                    help="JSON file with the language model's layer / unit / att_unit / head / embed_unit (default: 16 / 2048 / 512 / 8 / 128)")
     p.add_argument("--lm-weight", type=float, default=0.0, help="weight of the language model's log-probabilities (0: no fusion)")
+    p.add_argument("--decode-mode", choices=["search", "rescore"], default="search",
+                   help="search: the reference's label-synchronous hybrid CTC / attention beam search (default).  rescore: two-pass "
+                        "decoding -- a CTC prefix beam search on the device, then one teacher-forced decoder (+ LM) pass over its n-best")
+    p.add_argument("--rescore-beam", type=int, default=16, help="--decode-mode rescore: beam (and n-best) of the first pass, 2 .. 64")
+    p.add_argument("--rescore-topk", type=int, default=16, help="--decode-mode rescore: non-blank tokens considered per frame, 1 .. 32")
     return p.parse_args(argv)
 
 

@@ -264,6 +264,28 @@ int64_t avsr_ctc_align_workspace_bytes(int B, int T, int Lmax);
 int avsr_ctc_align(const void* logits, int dtype, int64_t ld, const int64_t* labels, int Lmax, int ignore_id,
                    const int64_t* in_lens, int blank, int32_t* ali, float* score, void* workspace, int B, int T,
                    int V, avsr_stream_t stream);
+/* CTC prefix beam search (ctc_beam.hip; not in the reference): the time-synchronous first pass of two-pass decoding.  lp f32
+ * [B][T][ld]: log-posteriors (columns [V, ld) ignored); in_lens int64 [B] (frames t >= in_lens[b] are not read).  A hypothesis is
+ * (prefix, pb, pnb); every frame considers blank plus the K non-blank tokens of largest lp[t] (1 <= K <= 32, K <= V - 1), merges
+ * the contributions that denote the same prefix and keeps the W (2 <= W <= 64) prefixes of largest logaddexp(pb, pnb).  Outputs,
+ * the nbest <= W prefixes by final total, best first: tokens int32 [B][nbest][T] padded with -1, lens int32 [B][nbest], score /
+ * pb / pnb f32 [B][nbest] (-inf beyond n_valid[b]), n_valid int32 [B].  in_lens[b] <= 0: one empty hypothesis with score 0.
+ * The workspace (avsr_ctc_beam_workspace_bytes, 16-byte aligned) keeps the whole history of the search, in this order:
+ *   tok  int32 [B][T][K]   the K tokens of each frame, by decreasing lp        val  f32 [B][T][K]  their lp
+ *   blk  f32   [B][T]      lp[t][blank]                                        cnt  int32 [B][T]   beam entries after frame t
+ *   node int32 [B][T*W+1][2]  (parent node, token) of node id n; node 0 is the empty prefix, the prefix that enters the beam
+ *                          at frame t in slot r as an extension gets id 1 + t*W + r
+ *   beam int32 [B][T][W][4]  per slot after frame t: node id, prefix length, pb, pnb (the last two f32 bits) */
+int64_t avsr_ctc_beam_workspace_bytes(int B, int T, int W, int K);
+int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest, int32_t* tokens,
+                         int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid, void* workspace, int B, int T,
+                         int V, avsr_stream_t stream);
+/* Exact CTC log-likelihood of N label sequences per utterance against ONE copy of its log-posteriors: lp f32 [B][T][ld]; labels
+ * int64 [B][N][Lmax] padded with ignore_id (Lmax <= 255); loglik f32 [B][N] = log P_ctc(labels | lp[b, :in_lens[b]]); no labels:
+ * the sum of lp[t][blank]; a sequence that does not fit the frames: -inf. */
+int64_t avsr_ctc_score_workspace_bytes(int B, int N, int T, int Lmax);
+int avsr_ctc_score(const float* lp, int64_t ld, const int64_t* labels, int N, int Lmax, int ignore_id, const int64_t* in_lens,
+                   int blank, float* loglik, void* workspace, int B, int T, int V, avsr_stream_t stream);
 /* label-smoothing KL (label_smoothing_loss.py:41-63) per row + argmax hit (nets_utils.py:272-292);
  * grad = softmax - smoothed target (zero rows for ignored targets; pad columns [V, ldg) written as zeros), may be NULL */
 int avsr_ce_smooth(const void* logits, int dtype, int64_t ld, const int64_t* target, int ignore_id, int V,

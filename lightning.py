@@ -244,8 +244,13 @@ class ModelModule(_Base):
         --lm-weight), when present, put a Transformer LM into the reference's `lm` slot (shallow fusion).  The LM is loaded once."""
         args = getattr(self, "args", None)
         lm_path, lm_weight = getattr(args, "lm_path", None), float(getattr(args, "lm_weight", 0.0) or 0.0)
+        make = get_beam_search_decoder
+        if getattr(args, "decode_mode", "search") == "rescore":  # eval.py --decode-mode rescore: two-pass decoding
+            def make(model, token_list, **kw):
+                return get_two_pass_decoder(model, token_list, beam_size=int(getattr(args, "rescore_beam", None) or 16),
+                                            topk=int(getattr(args, "rescore_topk", None) or 16), **kw)
         if not lm_path or lm_weight == 0.0:
-            return get_beam_search_decoder(self.model, self.token_list)
+            return make(self.model, self.token_list)
         cached = getattr(self, "_lm", None)
         if cached is None or cached[0] != (lm_path, getattr(args, "lm_conf", None)):
             from auto_avsr_amd.lm import TransformerLM
@@ -253,7 +258,7 @@ class ModelModule(_Base):
             lm = TransformerLM.from_files(len(self.token_list), lm_path, getattr(args, "lm_conf", None),
                                           device=next(self.model.parameters()).device)
             cached = self._lm = ((lm_path, getattr(args, "lm_conf", None)), [lm])  # (in a list: not a sub-module, not in state_dict)
-        return get_beam_search_decoder(self.model, self.token_list, rnnlm=cached[1][0], lm_weight=lm_weight)
+        return make(self.model, self.token_list, rnnlm=cached[1][0], lm_weight=lm_weight)
 
     def forward(self, sample):
         self.beam_search = self._make_beam_search()
@@ -278,6 +283,45 @@ class ModelModule(_Base):
         if HAVE_LIGHTNING:
             self.log("wer", wer)
         return wer
+
+
+def _resolve_lm(model, token_list, rnnlm, rnnlm_conf, lm_weight, what="search"):
+    """The `lm` slot of the decoders below: None, or a TransformerLM over the token list's vocabulary."""
+    lm = None
+    if rnnlm is not None and lm_weight != 0.0:
+        from auto_avsr_amd.lm import TransformerLM
+
+        if isinstance(rnnlm, TransformerLM):
+            lm = rnnlm
+        elif isinstance(rnnlm, (str, bytes)) or hasattr(rnnlm, "__fspath__"):
+            lm = TransformerLM.from_files(len(token_list), rnnlm, rnnlm_conf, device=next(model.parameters()).device)
+        else:
+            raise TypeError("rnnlm: a TransformerLM or the path of its state dict")
+        if lm.n_vocab != len(token_list):
+            raise ValueError(f"the language model's vocabulary ({lm.n_vocab}) is not the token list's ({len(token_list)})")
+    elif lm_weight != 0.0:
+        import warnings
+
+        warnings.warn(f"lm_weight={lm_weight} without a language model (rnnlm is None): the {what} runs without fusion")
+    return lm
+
+
+def get_two_pass_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight=0.1, lm_weight=0.0, beam_size=16,
+                         topk=16, nbest=None):
+    """Not in the reference: the scorers and weights of get_beam_search_decoder behind auto_avsr_amd.two_pass.TwoPassDecoder -- a
+    CTC prefix beam search on the device (beam_size entries, topk tokens per frame) whose nbest (default: all beam_size) are
+    rescored by one teacher-forced decoder (+ language model) pass under the same objective."""
+    from auto_avsr_amd.two_pass import TwoPassDecoder
+    from espnet.nets.scorers.length_bonus import LengthBonus
+
+    lm = _resolve_lm(model, token_list, rnnlm, rnnlm_conf, lm_weight, what="rescoring")
+    sos = eos = model.odim - 1
+    scorers = model.scorers()
+    scorers["lm"] = lm
+    scorers["length_bonus"] = LengthBonus(len(token_list))
+    weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight if lm is not None else 0.0, "length_bonus": penalty}
+    return TwoPassDecoder(scorers, weights, sos=sos, eos=eos, token_list=token_list, beam_size=beam_size, topk=topk, nbest=nbest,
+                          blank=model.blank, ignore_id=model.ignore_id)
 
 
 def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight=0.1, lm_weight=0.0,

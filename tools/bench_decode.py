@@ -26,9 +26,25 @@ def main():
                          "weights), lm_weight 0.3 -- native step, python-issued step with the "
                          "cached TransformerLM, python-issued step with a plain-torch LM as a foreign scorer (what a build without the LM slot "
                          "can do)")
+    ap.add_argument("--two-pass", action="store_true",
+                    help="two-pass decoding rows instead of the default ones: CTC prefix beam search on the device + one teacher-forced "
+                         "rescoring pass (auto_avsr_amd/two_pass.py) beside the native one-call search at --beam, on the same encoder "
+                         "outputs -- per phase at one utterance, and utterances/s at 1, 8 and 32 utterances per launch")
+    ap.add_argument("--two-pass-sweep", action="store_true",
+                    help="(beam, topk) sweep of two-pass decoding on the trained fixture of tests/test_wer_trained.py: WER, containment of "
+                         "the reference's best hypothesis in the n-best, share of utterances whose winner scores at least the reference's")
+    ap.add_argument("--two-pass-once", type=int, default=0, metavar="T",
+                    help="one warm-up and one two-pass decode of a T-frame utterance and nothing else (the program of a kernel-trace run)")
+    ap.add_argument("--rescore-beam", type=int, default=16)
+    ap.add_argument("--rescore-topk", type=int, default=16)
+    ap.add_argument("--modes", type=str, default="precise", help="--two-pass: comma-separated numerical modes (eval.py decodes in precise)")
     args = ap.parse_args()
     if args.lm:
         return main_lm(args)
+    if args.two_pass_sweep:
+        return main_two_pass_sweep(args)
+    if args.two_pass or args.two_pass_once:
+        return main_two_pass(args)
     import lightning
     from synth import synth_batch, synth_state_dict
 
@@ -235,6 +251,142 @@ def main_lm(args):
     AF.set_mode("bf16")
     print(json.dumps({"metric": "beam search with Transformer-LM shallow fusion, video E2E 250M decoder + 16 x 512 LM, beam search only (encoder output ready)",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def _timed(fn, reps):
+    """Median / min / max wall time in ms of fn() between device synchronisations, after one warm-up call."""
+    import statistics
+
+    ts, out = [], None
+    for rep in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            out = fn()
+        torch.cuda.synchronize()
+        if rep:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}, out
+
+
+def main_two_pass(args):
+    import lightning
+    from synth import synth_batch, synth_state_dict
+
+    from auto_avsr_amd import decoding
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+
+    dev = torch.device("cuda:0")
+    m = E2E(5049, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    toks = [str(i) for i in range(5049)]
+    bs = lightning.get_beam_search_decoder(m, toks, beam_size=args.beam)
+    tp = lightning.get_two_pass_decoder(m, toks, beam_size=args.rescore_beam, topk=args.rescore_topk)
+    decoding.NATIVE_BEAM = True
+
+    def encode(T, seed):
+        x, _, _ = synth_batch("video", 1, T, 3, 5049, seed=seed, lengths=[T])
+        with torch.no_grad():
+            return m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float()
+
+    if args.two_pass_once:
+        AF.set_mode("precise")
+        enc = encode(args.two_pass_once, args.two_pass_once)
+        for _ in range(2):
+            with torch.no_grad():
+                nbest = tp(enc)
+            torch.cuda.synchronize()
+        print(json.dumps({"T_frames": args.two_pass_once, "hypotheses": len(nbest), "best_tokens": len(nbest[0].yseq) - 2}))
+        return
+    rows = []
+    for mode in args.modes.split(","):
+        AF.set_mode(mode)
+        AF.invalidate_weight_cache()
+        bs._native = None
+        for T in (100, 400):
+            enc = encode(T, T)
+            t_native, nbest = _timed(lambda: bs(enc), args.reps)
+            assert bs._native
+            steps = max(len(h.asdict()["yseq"]) for h in nbest) - 1
+            # the phases of one two-pass decode, each between synchronisations
+            t_post, (memory, hlens, lp) = _timed(lambda: tp._posteriors([enc]), args.reps)
+            t_first, (labels, n_valid) = _timed(lambda: tp.first_pass(lp, hlens), args.reps)
+            t_ctc, _ = _timed(lambda: AF.ctc_score(lp, labels, hlens), args.reps)
+            t_all, _ = _timed(lambda: tp.score_labels(memory, hlens, lp, labels), args.reps)
+            t_total, two = _timed(lambda: tp(enc), args.reps)
+            rows.append({"mode": mode, "T_frames": T, "utterances_per_launch": 1, "native_search": {"beam": args.beam, "ms": t_native, "longest_hypothesis_tokens": steps,
+                                                                                                   "ms_per_token": round(t_native["median"] / max(steps, 1), 3)},
+                         "two_pass": {"beam": tp.beam_size, "topk": tp.topk, "nbest": tp.nbest, "n_valid": int(n_valid[0]), "longest_label_row": int(labels.shape[2]),
+                                      "ctc_posteriors_ms": t_post, "first_pass_ms": t_first, "ctc_score_ms": t_ctc,
+                                      "rescoring_ms_decoder_plus_ctc_score": t_all, "whole_decode_ms": t_total},
+                         "speedup_whole_decode_over_native_search": round(t_native["median"] / t_total["median"], 2),
+                         "same_best_hypothesis": two[0].asdict()["yseq"] == nbest[0].asdict()["yseq"],
+                         "two_pass_best_score": round(float(two[0].score), 4), "native_best_score": round(float(nbest[0].score), 4)})
+            print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+            for B in (8, 32):
+                encs = [enc] + [encode(T, 1000 + i) for i in range(B - 1)]
+                t_many, res = _timed(lambda: tp.forward_many(encs), max(1, args.reps - 1))
+                t_nat, _ = _timed(lambda: bs.forward_many(encs, workers=4), 1) if B == 8 else (None, None)
+                rows.append({"mode": mode, "T_frames": T, "utterances_per_launch": B, "two_pass_ms_total": t_many,
+                             "two_pass_utterances_per_sec": round(B / (t_many["median"] / 1e3), 2),
+                             "two_pass_utterances_per_sec_at_1": round(1e3 / t_total["median"], 2),
+                             "native_search_4_in_flight_ms_total": t_nat,
+                             "native_utterances_per_sec_4_in_flight": None if t_nat is None else round(B / (t_nat["median"] / 1e3), 2),
+                             "first_equals_single": res[0][0].asdict()["yseq"] == two[0].asdict()["yseq"]})
+                print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+                del encs
+    AF.set_mode("bf16")
+    print(json.dumps({"metric": "two-pass decoding (CTC prefix beam search on the device + teacher-forced rescoring) against the native one-call "
+                                "hybrid search, video E2E 250M, vocabulary 5049, search only (encoder output ready)",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def main_two_pass_sweep(args):
+    import lightning
+    import trained_common as TC
+    from synth import synth_state_dict
+
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+
+    fx = torch.load(TC.FIXTURE, weights_only=False)
+    m = E2E(TC.ODIM, "video", adim=TC.D, aheads=TC.H, eunits=TC.U, elayers=TC.NENC, dunits=TC.U, dlayers=TC.NDEC)
+    sd = synth_state_dict(m.state_dict(), TC.SEED)
+    sd.update(fx["weights"])
+    m.load_state_dict(sd, strict=True)
+    m = m.cuda().eval()
+    toks = [str(i) for i in range(TC.ODIM)]
+    AF.set_mode("precise")
+    encs = []
+    with torch.no_grad():
+        for i, u in enumerate(fx["utts"]):
+            encs.append(m.encoder(m.proj_encoder(m.frontend(TC.video(i, u["T"]).unsqueeze(0).cuda())), None)[0].squeeze(0).float())
+    rows = []
+    for W, K in ((8, 8), (16, 8), (16, 16), (32, 16)):
+        tp = lightning.get_two_pass_decoder(m, toks, beam_size=W, topk=K)
+        dist, contained, natural, ge, same = 0, 0, 0, 0, 0
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            out = tp.forward_many(encs)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        for u, nbest in zip(fx["utts"], out):
+            got, ref = nbest[0].asdict(), u["hyps"][0]
+            dist += TC.edit_distance(u["label"], [int(t) for t in got["yseq"][1:-1]])
+            natural += len(ref["yseq"]) - 2 < u["T"]
+            contained += any(h.yseq.tolist() == ref["yseq"] for h in nbest)
+            ge += got["score"] >= ref["score"] - 1e-3 * max(1.0, abs(ref["score"]))
+            same += got["yseq"] == ref["yseq"]
+        n = len(fx["utts"])
+        rows.append({"beam": W, "topk": K, "nbest": W, "wer": round(dist / fx["total_length"], 4), "reference_search_wer": round(fx["wer"], 4),
+                     "utterances": n, "reference_best_natural_ended": natural, "reference_best_in_nbest": contained,
+                     "winner_scores_at_least_reference_best": ge, "winner_is_reference_best": same,
+                     "one_launch_ms_all_utterances_incl_first_call_overheads": round(dt * 1e3, 1)})
+        print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    AF.set_mode("bf16")
+    print(json.dumps({"metric": "two-pass decoding on the trained fixture (32 utterances, T = 12 ... 400, reference search: beam 40)", "rows": rows}))
 
 
 if __name__ == "__main__":
