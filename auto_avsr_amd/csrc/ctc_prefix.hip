@@ -31,12 +31,11 @@ AVSR_DEV float logaddexp2(float a, float b) {
 #endif
 }
 
-__global__ __launch_bounds__(64) void ctc_prefix_kernel(const float* __restrict__ logp, int T, int ldv,
-                                                         const float* __restrict__ r_prev, const int64_t* __restrict__ last,
-                                                         const int64_t* __restrict__ cand, int NH, int S, int out_len,
-                                                         int blank, float* __restrict__ r_new, float* __restrict__ psi,
-                                                         float* __restrict__ psi_eos) {
-    const int id = blockIdx.x * 64 + threadIdx.x;  // (one wave per block: 2 400 chains spread over 38 CUs instead of 10)
+// the chain of pair `id` = (hypothesis id / S, candidate id % S) of ONE utterance
+AVSR_DEV void ctc_prefix_chain(const float* __restrict__ logp, int T, int ldv, const float* __restrict__ r_prev,
+                               const int64_t* __restrict__ last, const int64_t* __restrict__ cand, int NH, int S, int out_len,
+                               int blank, float* __restrict__ r_new, float* __restrict__ psi, float* __restrict__ psi_eos,
+                               int id) {
     if (id >= NH * S) return;
     const int n = id / S, s = id - n * S;
     const int c = (int)cand[id];
@@ -90,6 +89,40 @@ __global__ __launch_bounds__(64) void ctc_prefix_kernel(const float* __restrict_
     psi[id] = pm + logf(ps);
 }
 
+__global__ __launch_bounds__(64) void ctc_prefix_kernel(const float* __restrict__ logp, int T, int ldv,
+                                                         const float* __restrict__ r_prev, const int64_t* __restrict__ last,
+                                                         const int64_t* __restrict__ cand, int NH, int S, int out_len,
+                                                         int blank, float* __restrict__ r_new, float* __restrict__ psi,
+                                                         float* __restrict__ psi_eos) {
+    // (one wave per block: 2 400 chains spread over 38 CUs instead of 10)
+    ctc_prefix_chain(logp, T, ldv, r_prev, last, cand, NH, S, out_len, blank, r_new, psi, psi_eos, blockIdx.x * 64 + threadIdx.x);
+}
+
+// The same chains for a GROUP of utterances in one launch: utterance u owns the packed hypothesis rows [off, off + n) of last /
+// cand / psi / psi_eos, its own posteriors, length and state regions, and the blocks [blk0, blk0 + ceil(n * S / 64)) -- a block
+// never holds chains of two utterances, a chain computes what ctc_prefix_kernel computes for its utterance alone.
+constexpr int CTC_MAX_UTT = 32;
+struct CtcUtt {
+    const float* logp;    // [T][ldv]
+    const float* r_prev;  // [T][2][n]
+    float* r_new;         // [T][2][n][S]
+    int T, ldv, off, n, blk0;
+};
+struct CtcGroup {
+    int U;
+    CtcUtt u[CTC_MAX_UTT];
+};
+
+__global__ __launch_bounds__(64) void ctc_prefix_batch_kernel(CtcGroup g, const int64_t* __restrict__ last,
+                                                               const int64_t* __restrict__ cand, int S, int out_len, int blank,
+                                                               float* __restrict__ psi, float* __restrict__ psi_eos) {
+    int u = 0;
+    while (u + 1 < g.U && (int)blockIdx.x >= g.u[u + 1].blk0) u++;
+    const CtcUtt& d = g.u[u];
+    ctc_prefix_chain(d.logp, d.T, d.ldv, d.r_prev, last + d.off, cand + (size_t)d.off * S, d.n, S, out_len, blank, d.r_new,
+                     psi + (size_t)d.off * S, psi_eos + d.off, ((int)blockIdx.x - d.blk0) * 64 + threadIdx.x);
+}
+
 }  // namespace
 
 // logp: [T][ldv] f32 log-softmax rows of ONE utterance; r_prev: [T][2][NH] (state of the running hypotheses: log prob of
@@ -104,5 +137,41 @@ extern "C" int avsr_ctc_prefix_score(const float* logp, int T, int V, int ldv, c
     AVSR_LAUNCH(ctc_prefix_kernel, dim3((NH * S + 63) / 64), dim3(64), 0, stream, logp, T, ldv, r_prev, last, cand, NH, S,
                 out_len, blank, r_new, psi, psi_eos);
     AVSR_CHECK_LAUNCH("ctc_prefix_score");
+    return 0;
+}
+
+// The same for a group of U <= 32 utterances whose running hypotheses are ONE packed row list (all prefixes of the same length):
+// utterance u owns rows [row_off[u], row_off[u] + n_rows[u]) of last / cand [rows][S] / psi [rows][S] / psi_eos [rows] (n_rows[u] == 0:
+// nothing runs for it), scores them against its own logp[u] [T[u]][ldv[u]]; with F = frame_off[u] (the frames of the utterances
+// before it) its state is r_prev + 2 * F * pitch laid out [T[u]][2][n_rows[u]], its output r_new + 2 * F * pitch * S laid out
+// [T[u]][2][n_rows[u]][S] (pitch >= every n_rows[u]: the rows an utterance may ever hold).  All arrays of length U are host memory.
+extern "C" int avsr_ctc_prefix_score_batch(int U, const float* const* logp, const int32_t* T, const int32_t* ldv, int V,
+                                           const float* r_prev, const int64_t* last, const int64_t* cand, const int32_t* row_off,
+                                           const int32_t* n_rows, const int64_t* frame_off, int pitch, int S, int out_len, int blank,
+                                           float* r_new, float* psi, float* psi_eos, hipStream_t stream) {
+    AVSR_REQUIRE(U >= 1 && U <= CTC_MAX_UTT && V > 0 && blank >= 0 && blank < V && out_len >= 0 && S > 0 && pitch > 0,
+                 "ctc_prefix_score_batch: bad dimensions (at most 32 utterances)");
+    CtcGroup g;
+    g.U = 0;
+    int blocks = 0;
+    for (int u = 0; u < U; u++) {
+        AVSR_REQUIRE(T[u] > 0 && ldv[u] >= V && n_rows[u] >= 0 && n_rows[u] <= pitch && row_off[u] >= 0 && frame_off[u] >= 0,
+                     "ctc_prefix_score_batch: bad utterance descriptor");
+        if (n_rows[u] == 0) continue;
+        CtcUtt& d = g.u[g.U++];
+        d.logp = logp[u];
+        d.r_prev = r_prev + (size_t)2 * frame_off[u] * pitch;
+        d.r_new = r_new + (size_t)2 * frame_off[u] * pitch * S;
+        d.T = T[u];
+        d.ldv = ldv[u];
+        d.off = row_off[u];
+        d.n = n_rows[u];
+        d.blk0 = blocks;
+        blocks += (n_rows[u] * S + 63) / 64;
+    }
+    if (g.U == 0) return 0;
+    for (int u = g.U; u < CTC_MAX_UTT; u++) g.u[u] = CtcUtt{nullptr, nullptr, nullptr, 0, 0, 0, 0, blocks};
+    AVSR_LAUNCH(ctc_prefix_batch_kernel, dim3(blocks), dim3(64), 0, stream, g, last, cand, S, out_len, blank, psi, psi_eos);
+    AVSR_CHECK_LAUNCH("ctc_prefix_score_batch");
     return 0;
 }

@@ -53,6 +53,26 @@ struct IdxList {
     int idx[MAX_BEAM];
 };
 
+// A GROUP of utterances decoded together (avsr_beam_*_batch): the running hypotheses of all of them are one packed row list, every
+// utterance at the same position L.  Utterance u owns rows [off, off + n) of the current beam and rows [noff, noff + nn) of the
+// beam a kernel writes; f0 = frames of the utterances before it (its memory K / V, CTC state and r_new regions start there);
+// g0 = its first block of the source attention.  Passed to the kernels by value (1 KB of kernel arguments).
+constexpr int MAX_UTT = 32, MAX_ROWS = 1024;
+struct Utt {
+    int off, n, noff, nn, T, g0;
+    long f0;
+};
+struct Group {
+    int U, rows, blocks, spare;  // rows of the current beam, blocks of the source attention
+    Utt u[MAX_UTT];
+};
+struct RowList {
+    unsigned short from[MAX_ROWS];
+};
+struct PtrList {
+    const float* p[MAX_UTT];
+};
+
 AVSR_DEV float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
@@ -162,22 +182,24 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(const float* __restrict_
 // block the 480 blocks of a beam-40 step pull 98 MB through the L2s at T = 400: 35 us per launch).  Layout as dec_attn_kernel:
 // 16 lanes per key, 16 keys per block iteration, four iterations' loads in flight; wave w owns the softmax of hypothesis w.
 constexpr int SRC_HB = 4;
-__global__ __launch_bounds__(1024) void dec_src_attn_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ kv, long step_j,
-                                                           int voff, int n, int len, float scale, float* __restrict__ out, long ldo) {
-    AVSR_DYN_SMEM(smem);
-    const int nwv = blockDim.x >> 6;             // 4, 8 or 16 waves
+// rows [b0, min(b0 + SRC_HB, n)) against `len` keys with nwv waves.  GROUPED: the block may have more waves than nwv (a launch
+// over utterances of different lengths has the block size of the longest); the spare waves only meet the barriers, so that keys are
+// dealt to waves and partial sums are added exactly as in a launch of nwv waves.
+template <bool GROUPED>
+AVSR_DEV void src_attn_block(char* smem, float* s_l, const float* __restrict__ q, long ldq, const float* __restrict__ kv, long step_j, int voff,
+                             int b0, int n, int len, int nwv, float scale, float* __restrict__ out, long ldo) {
     float* sc = reinterpret_cast<float*>(smem);  // [SRC_HB][len]
     float* part = sc + SRC_HB * len;             // [nwv][SRC_HB][64]
-    __shared__ float s_l[SRC_HB];
-    const int b0 = blockIdx.x * SRC_HB, h = blockIdx.y;
+    const int h = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool busy = !GROUPED || wave < nwv;
     const int g = lane >> 4, c = lane & 15;
     f32x4 q4[SRC_HB];
 #pragma unroll
     for (int i = 0; i < SRC_HB; i++)
         q4[i] = b0 + i < n ? *reinterpret_cast<const f32x4*>(q + (size_t)(b0 + i) * ldq + h * 64 + 4 * c) : f32x4{0.f, 0.f, 0.f, 0.f};
     const float* base = kv + h * 64 + 4 * c;
-    for (int j0 = 0; j0 < len; j0 += 16 * nwv) {
+    for (int j0 = 0; busy && j0 < len; j0 += 16 * nwv) {
         f32x4 k4[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -215,7 +237,7 @@ __global__ __launch_bounds__(1024) void dec_src_attn_kernel(const float* __restr
     f32x4 acc[SRC_HB];
 #pragma unroll
     for (int i = 0; i < SRC_HB; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int j0 = 0; j0 < len; j0 += 16 * nwv) {
+    for (int j0 = 0; busy && j0 < len; j0 += 16 * nwv) {
         f32x4 v4[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -242,7 +264,7 @@ __global__ __launch_bounds__(1024) void dec_src_attn_kernel(const float* __restr
             acc[i][e] += __shfl_xor(acc[i][e], 16);
             acc[i][e] += __shfl_xor(acc[i][e], 32);
         }
-    if (g == 0) {
+    if (g == 0 && busy) {
 #pragma unroll
         for (int i = 0; i < SRC_HB; i++)
 #pragma unroll
@@ -257,6 +279,28 @@ __global__ __launch_bounds__(1024) void dec_src_attn_kernel(const float* __restr
             out[(size_t)(b0 + i) * ldo + h * 64 + d] = v / s_l[i];
         }
     }
+}
+
+__global__ __launch_bounds__(1024) void dec_src_attn_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ kv, long step_j,
+                                                           int voff, int n, int len, float scale, float* __restrict__ out, long ldo) {
+    AVSR_DYN_SMEM(smem);
+    __shared__ float s_l[SRC_HB];
+    src_attn_block<false>(smem, s_l, q, ldq, kv, step_j, voff, blockIdx.x * SRC_HB, n, len, blockDim.x >> 6 /* 4, 8 or 16 waves */, scale, out, ldo);
+}
+
+// The same for a group of utterances: block x belongs to the utterance whose block range [g0, ...) holds it, takes SRC_HB of ITS
+// rows (a block never holds rows of two utterances) against ITS memory projection kv + f0 * step_j and length, with the wave count
+// a launch for that length alone would have.  Dynamic LDS is sized for the longest utterance.
+__global__ __launch_bounds__(1024) void dec_src_attn_group_kernel(Group grp, const float* __restrict__ q, long ldq, const float* __restrict__ kv,
+                                                                 long step_j, int voff, float scale, float* __restrict__ out, long ldo) {
+    AVSR_DYN_SMEM(smem);
+    __shared__ float s_l[SRC_HB];
+    int u = 0;
+    while (u + 1 < grp.U && (int)blockIdx.x >= grp.u[u + 1].g0) u++;
+    const Utt d = grp.u[u];
+    const int nwv = d.T <= 64 ? 4 : (d.T <= 256 ? 8 : 16);
+    src_attn_block<true>(smem, s_l, q, ldq, kv + (size_t)d.f0 * step_j, step_j, voff, d.off + ((int)blockIdx.x - d.g0) * SRC_HB, d.off + d.n, d.T,
+                         nwv, scale, out, ldo);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -744,15 +788,14 @@ struct SelectArgs {
     float* selv;  // [K][4]: total, decoder term logp, ctc term (log_psi - s_prev), ctc log_psi
 };
 
-__global__ __launch_bounds__(SEL_NT) void beam_select_kernel(SelectArgs a) {
-    AVSR_DYN_SMEM(smem);
+// row0: the packed row of the utterance's hypothesis 0 (what `prev` counts from; 0 for a search of one utterance)
+AVSR_DEV void beam_select_block(char* smem, RadixScratch& sc, const SelectArgs& a, int row0) {
     const int NE = a.n * (a.S + 1);
     float* val = reinterpret_cast<float*>(smem);            // [NE]
     unsigned* keys = reinterpret_cast<unsigned*>(val + NE);  // [NE]
     int* picked = reinterpret_cast<int*>(keys + NE);         // [K]
     int* cnd = picked + a.K;                                 // [n][S] candidate tokens
     int* has_eos = cnd + a.n * a.S;                          // [n] <eos> is among the candidates of hypothesis b
-    __shared__ RadixScratch sc;
     const int tid = threadIdx.x;
     for (int i = tid; i < a.n; i += SEL_NT) has_eos[i] = 0;
     __syncthreads();
@@ -809,7 +852,7 @@ __global__ __launch_bounds__(SEL_NT) void beam_select_kernel(SelectArgs a) {
         int b, c, tok;
         float dec, ctc_rel, log_psi;
         decode(e, b, c, tok, dec, ctc_rel, log_psi);
-        a.sel[4 * rank + 0] = b;
+        a.sel[4 * rank + 0] = row0 + b;
         a.sel[4 * rank + 1] = tok;
         a.sel[4 * rank + 2] = c;
         a.sel[4 * rank + 3] = 0;
@@ -818,6 +861,32 @@ __global__ __launch_bounds__(SEL_NT) void beam_select_kernel(SelectArgs a) {
         a.selv[4 * rank + 2] = ctc_rel;
         a.selv[4 * rank + 3] = log_psi;
     }
+}
+
+__global__ __launch_bounds__(SEL_NT) void beam_select_kernel(SelectArgs a) {
+    AVSR_DYN_SMEM(smem);
+    __shared__ RadixScratch sc;
+    beam_select_block(smem, sc, a, 0);
+}
+
+// One block per utterance of a group on that utterance's entries: `a` describes the packed tables (row 0 of the group), the block
+// moves to its own rows.  K best of the utterance's n * (S + 1) entries, same order of additions, same tie rule.
+__global__ __launch_bounds__(SEL_NT) void beam_select_group_kernel(SelectArgs a, Group grp) {
+    AVSR_DYN_SMEM(smem);
+    __shared__ RadixScratch sc;
+    const Utt d = grp.u[blockIdx.x];
+    if (d.n == 0) return;
+    a.logp += (size_t)d.off * a.ld;
+    if (a.lm_logp) a.lm_logp += (size_t)d.off * a.ld;
+    a.cand += (size_t)d.off * a.S;
+    a.psi += (size_t)d.off * a.S;
+    a.psi_eos += d.off;
+    a.s_prev += d.off;
+    a.score += d.off;
+    a.n = d.n;
+    a.sel += 4 * d.noff;
+    a.selv += 4 * d.noff;
+    beam_select_block(smem, sc, a, d.off);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -831,12 +900,13 @@ struct BeamBuf {
 };
 
 // new hypothesis k = hypothesis prev[k] extended by tok[k]  (batch_beam_search.py:131-176 merge + select states)
-__global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf dst, int ldy, int beam, int L, int n_src, int K, int T, int S,
-                                                          const int* __restrict__ sel, const float* __restrict__ selv,
-                                                          const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
-                                                          float* __restrict__ host_row) {
-    const int k = blockIdx.x, tid = threadIdx.x;
-    const int prev = sel[4 * k], tok = sel[4 * k + 1];
+// k, prev: rows of the tables (pitch `beam` of the scalars); kl, pl: the same hypotheses counted within their utterance, whose CTC
+// state is r_new [T][2][n_src][S] -> dst_r [T][2][K]
+AVSR_DEV void beam_update_row(const BeamBuf& src, const BeamBuf& dst, int ldy, int beam, int L, int n_src, int K, int T, int S, int k, int kl,
+                              int row0, const int* __restrict__ sel, const float* __restrict__ selv, const float* __restrict__ r_new,
+                              float* __restrict__ dst_r, const float* __restrict__ lm_logp, long ld_lm, float* __restrict__ host_row) {
+    const int tid = threadIdx.x;
+    const int prev = sel[4 * k], tok = sel[4 * k + 1], pl = prev - row0;
     int pos = sel[4 * k + 2];
     if (pos < 0) pos = S - 1;  // <eos> outside the candidates: the hypothesis ends here, its CTC state is never read
     for (int j = tid; j < L; j += 256) {
@@ -867,7 +937,33 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf d
         h[7] = 0.f;
     }
     // CTC forward variables of (prev, candidate column pos): r_new [T][2][n_src][S] -> dst.r [T][2][K]
-    for (int i = tid; i < 2 * T; i += 256) dst.r[(size_t)i * K + k] = r_new[((size_t)i * n_src + prev) * S + pos];
+    for (int i = tid; i < 2 * T; i += 256) dst_r[(size_t)i * K + kl] = r_new[((size_t)i * n_src + pl) * S + pos];
+}
+
+__global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf dst, int ldy, int beam, int L, int n_src, int K, int T, int S,
+                                                          const int* __restrict__ sel, const float* __restrict__ selv,
+                                                          const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
+                                                          float* __restrict__ host_row) {
+    beam_update_row(src, dst, ldy, beam, L, n_src, K, T, S, blockIdx.x, blockIdx.x, 0, sel, selv, r_new, dst.r, lm_logp, ld_lm, host_row);
+}
+
+// the utterance that owns row k of the beam being written
+AVSR_DEV int utt_of_new_row(const Group& g, int k) {
+    int u = 0;
+    while (u + 1 < g.U && k >= g.u[u + 1].noff) u++;
+    return u;
+}
+
+// group form: block = new packed row; the scalars have pitch `pitch` (the group's rows), an utterance's CTC regions the pitch
+// `beam` rows per frame: r at 2 * f0 * beam, r_new at 2 * f0 * beam * S
+__global__ __launch_bounds__(256) void beam_update_group_kernel(BeamBuf src, BeamBuf dst, Group grp, int ldy, int pitch, int beam, int L, int S,
+                                                                const int* __restrict__ sel, const float* __restrict__ selv,
+                                                                const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
+                                                                float* __restrict__ host_row) {
+    const int k = blockIdx.x;
+    const Utt d = grp.u[utt_of_new_row(grp, k)];
+    beam_update_row(src, dst, ldy, pitch, L, d.n, d.nn, d.T, S, k, k - d.noff, d.off, sel, selv, r_new + (size_t)2 * d.f0 * beam * S,
+                    dst.r + (size_t)2 * d.f0 * beam, lm_logp, ld_lm, host_row);
 }
 
 // hypotheses keep.idx[0 .. keep.n) survive (ended ones are taken off the beam, batch_beam_search.py:178-206)
@@ -882,6 +978,22 @@ __global__ __launch_bounds__(256) void beam_keep_kernel(BeamBuf src, BeamBuf dst
     for (int i = tid; i < 2 * T; i += 256) dst.r[(size_t)i * keep.n + k] = src.r[(size_t)i * n_src + from];
 }
 
+// group form: new packed row k = current packed row keep.from[k] (of the same utterance); utterance u goes from n to nn rows
+__global__ __launch_bounds__(256) void beam_keep_group_kernel(BeamBuf src, BeamBuf dst, Group grp, int ldy, int pitch, int beam, int L, RowList keep) {
+    const int k = blockIdx.x, tid = threadIdx.x, from = keep.from[k];
+    const Utt d = grp.u[utt_of_new_row(grp, k)];
+    for (int j = tid; j < L; j += 256) {
+        dst.yseq[(size_t)k * ldy + j] = src.yseq[(size_t)from * ldy + j];
+        if (j < L - 1) dst.anc[(size_t)k * ldy + j] = src.anc[(size_t)from * ldy + j];
+    }
+    if (tid < 6) dst.sc[tid * pitch + k] = src.sc[tid * pitch + from];
+    if (tid == 6) dst.last[k] = src.last[from];
+    const float* sr = src.r + (size_t)2 * d.f0 * beam;
+    float* dr = dst.r + (size_t)2 * d.f0 * beam;
+    const int kl = k - d.noff, fl = from - d.off;
+    for (int i = tid; i < 2 * d.T; i += 256) dr[(size_t)i * d.nn + kl] = sr[(size_t)i * d.n + fl];
+}
+
 __global__ void beam_init_kernel(BeamBuf st, int beam, int T, int sos, const float* __restrict__ r_init) {
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
     if (tid == 0) {
@@ -890,6 +1002,18 @@ __global__ void beam_init_kernel(BeamBuf st, int beam, int T, int sos, const flo
         for (int i = 0; i < 6; i++) st.sc[i * beam] = 0.f;
     }
     if (tid < 2 * T) st.r[tid] = r_init[tid];
+}
+
+// group form: block (x, u); utterance u starts as the one row u
+__global__ void beam_init_group_kernel(BeamBuf st, Group grp, PtrList r_init, int ldy, int pitch, int beam, int sos) {
+    const int u = blockIdx.y, tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const Utt d = grp.u[u];
+    if (tid == 0) {
+        st.yseq[(size_t)d.off * ldy] = sos;
+        st.last[d.off] = sos;
+        for (int i = 0; i < 6; i++) st.sc[i * pitch + d.off] = 0.f;
+    }
+    if (tid < 2 * d.T) st.r[(size_t)2 * d.f0 * beam + tid] = r_init.p[u][tid];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -932,7 +1056,35 @@ struct Session {
     float *x, *x1, *x2, *h, *att, *q2, *ff, *part, *stx, *st1, *st2, *mean, *rstd, *logits, *logp, *lse, *psi, *psi_eos, *r_new, *selv, *host_dev;
     int64_t* cand;
     int* sel;
+    // a group of utterances (avsr_beam_begin_batch): U > 0, the tables above carved for U * beam rows and the frames of all of them
+    int U = 0, Tmax = 0;
+    Utt utt[MAX_UTT];  // off / n / T / f0 of every utterance (n == 0: retired); the per-launch fields are filled by group_of
+    const float* u_logp[MAX_UTT];
+    int32_t u_ld[MAX_UTT];
 };
+
+// the group's descriptor for the kernels of one step: rows of the current beam, `nn[u]` rows per utterance in the beam being written
+Group group_of(Session& s, const int* nn) {
+    Group g;
+    g.U = s.U;
+    int off = 0, noff = 0, g0 = 0;
+    for (int u = 0; u < MAX_UTT; u++) {
+        Utt d = u < s.U ? s.utt[u] : Utt{0, 0, 0, 0, 0, 0, 0};
+        d.off = off;
+        d.noff = noff;
+        d.nn = u < s.U ? nn[u] : 0;
+        d.g0 = g0;
+        off += d.n;
+        noff += d.nn;
+        g0 += (d.n + SRC_HB - 1) / SRC_HB;
+        g.u[u] = d;
+        if (u < s.U) s.utt[u].off = d.off;
+    }
+    g.rows = off;
+    g.blocks = g0;
+    g.spare = 0;
+    return g;
+}
 
 struct Carver {
     char* base;
@@ -945,8 +1097,10 @@ struct Carver {
     }
 };
 
-void carve(Session& s, Carver& c, int T, int Lmax) {
-    const size_t beam = s.beam, D = s.D;
+// rows: hypotheses the tables hold (beam; U * beam for a group), T: frames (of all utterances of a group: the per-utterance regions
+// of the CTC state, of r_new and of the memory projection lie behind one another, `beam` rows per frame)
+void carve(Session& s, Carver& c, size_t rows, size_t T, int Lmax) {
+    const size_t per = s.beam, beam = rows, D = s.D;
     const int ldy = Lmax + 2, ldv = (s.V + 7) / 8 * 8;
     s.ldy = ldy;
     s.ldv = ldv;
@@ -955,7 +1109,7 @@ void carve(Session& s, Carver& c, int T, int Lmax) {
         s.st[i].anc = c.take<int>(beam * ldy);
         s.st[i].last = c.take<int64_t>(beam);
         s.st[i].sc = c.take<float>(6 * beam);
-        s.st[i].r = c.take<float>((size_t)2 * T * beam);
+        s.st[i].r = c.take<float>((size_t)2 * T * per);
     }
     s.cache.resize(s.nl);
     s.memkv.resize(s.nl);
@@ -982,7 +1136,7 @@ void carve(Session& s, Carver& c, int T, int Lmax) {
     s.cand = c.take<int64_t>(beam * (size_t)s.S);
     s.psi = c.take<float>(beam * (size_t)s.S);
     s.psi_eos = c.take<float>(beam);
-    s.r_new = c.take<float>((size_t)2 * T * beam * s.S);
+    s.r_new = c.take<float>((size_t)2 * T * per * s.S);
     s.sel = c.take<int>(4 * beam);
     s.selv = c.take<float>(4 * beam);
     s.host_dev = c.take<float>(8 * beam);
@@ -1071,9 +1225,9 @@ void lm_release(Lm& m) { m.on = 0; }
 // The language model's pass over the new position of the n running hypotheses: log-probabilities of the next token into lm.logp
 // [n][ldv].  Same shape as the decoder's pass without source attention: 2 + 5 launches per layer (6 with a sliced second FFN
 // contraction) + 1.
-int lm_step(Session& s, const BeamBuf& st, int n, int L, hipStream_t stream) {
+int lm_step(Session& s, const BeamBuf& st, int n, int L, int pitch, hipStream_t stream) {
     Lm& m = s.lm;
-    const int D = m.D, beam = s.beam;
+    const int D = m.D, beam = pitch;  // slots per position of the cache
     const float scale = 1.0f / sqrtf(64.f);
     RowStats sx{m.stx, 1}, s1{m.st1, 0};
     AVSR_LAUNCH(lm_input_kernel, dim3(n), dim3(256), 0, stream, (const int64_t*)st.last, m.table, m.eg, m.eb, m.eps, m.pe + (size_t)(L - 1) * D,
@@ -1206,7 +1360,7 @@ extern "C" int avsr_beam_attach_lm(int64_t h, const int32_t* cfg, const float* f
 extern "C" int64_t avsr_beam_workspace_bytes(int64_t h, int T, int Lmax) {
     Session tmp = *reinterpret_cast<Session*>((intptr_t)h);
     Carver c{nullptr};
-    carve(tmp, c, T, Lmax);
+    carve(tmp, c, tmp.beam, T, Lmax);
     return (int64_t)c.off + 256;
 }
 
@@ -1218,8 +1372,9 @@ extern "C" int avsr_beam_begin(int64_t h, const float* memory, int T, const floa
     AVSR_REQUIRE(T >= 1 && Lmax >= 1 && Lmax + 1 <= s.pe_rows, "beam_begin: bad lengths (position table too short?)");
     AVSR_REQUIRE(!s.lm.on || Lmax + 1 <= s.lm.pe_rows, "beam_begin: the language model's position table is too short");
     Carver c{reinterpret_cast<char*>(ws)};
-    carve(s, c, T, Lmax);
+    carve(s, c, s.beam, T, Lmax);
     AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin: workspace too small");
+    s.U = 0;
     s.T = T;
     s.Lmax = Lmax;
     s.ctc_logp = ctc_logp;
@@ -1234,18 +1389,13 @@ extern "C" int avsr_beam_begin(int64_t h, const float* memory, int T, const floa
     return 0;
 }
 
-// One decoding step for the n running hypotheses (all of length L): decoder pass over the new position, pre-beam, CTC
-// prefix scores, top-K, new beam state.  host_out [K][8] f32: token, parent, total score, decoder / ctc / length-bonus
-// sums, language-model sum (0 without one), 0 -- valid on return (the call synchronises the stream).  Returns K through n_out.
-// With a language model attached its pass is issued first, in line on the same stream (DESIGN.md section 7).
-extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
-    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(s.n >= 1 && s.L <= s.Lmax, "beam_step: no running hypotheses / maximum length reached");
-    const int n = s.n, L = s.L, D = s.D, beam = s.beam;
-    BeamBuf& st = s.st[s.cur];
-    BeamBuf& nx = s.st[s.cur ^ 1];
+// The decoder's pass over the new position of the n running hypotheses (rows of st), L tokens each: log-probabilities into s.logp,
+// pre-beam candidates into s.cand.  pitch: slots per position of the K / V caches (beam; the rows of a group); grp: the utterances of
+// a group (s.T = the longest one's frames), NULL for a search of one utterance.
+static int dec_pass(Session& s, BeamBuf& st, int n, int L, int pitch, const Group* grp, hipStream_t stream) {
+    const int D = s.D, beam = pitch;  // slots per position of the cache
     const float scale = 1.0f / sqrtf(64.f);
-    if (s.lm.on) DEC_TRY(lm_step(s, st, n, L, stream));
+    if (s.lm.on) DEC_TRY(lm_step(s, st, n, L, pitch, stream));
     // embedding of the last token at position L - 1 (transformer_decoder.py:186-189, embedding.py:78-87) + its row statistics
     RowStats sx{s.stx, 1}, s1{s.st1, 0}, s2{s.st2, 0};
     AVSR_LAUNCH(dec_embed_kernel, dim3(n), dim3(256), 0, stream, (const int64_t*)st.last, s.embed, s.pe + (size_t)(L - 1) * D, s.emb_scale, D,
@@ -1260,8 +1410,12 @@ extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_
                     (const float*)s.cache[l], (long)beam * 3 * D, (long)3 * D, D, 2 * D, (const int*)st.anc, s.ldy, L, scale, s.att, (long)D);
         DEC_TRY(skinny(s.att, D, w.wo, n, D, D, w.bo, nullptr, nullptr, 0.f, nullptr, 0, x, D, s.x1, D, &s1, nullptr, stream));
         DEC_TRY(skinny(s.x1, D, w.wq2, n, D, D, w.bq2, w.n2g, w.n2b, s.eps, &s1, 0, nullptr, 0, s.q2, D, nullptr, nullptr, stream));
-        AVSR_LAUNCH(dec_src_attn_kernel, dim3((n + SRC_HB - 1) / SRC_HB, s.H), dim3(64 * wv_src), (size_t)SRC_HB * (s.T + 64 * wv_src) * sizeof(float), stream,
-                    (const float*)s.q2, (long)D, (const float*)s.memkv[l], (long)2 * D, D, n, s.T, scale, s.att, (long)D);
+        if (grp) {  // (block size and LDS of the longest utterance; every block works with the waves of its own)
+            AVSR_LAUNCH(dec_src_attn_group_kernel, dim3(grp->blocks, s.H), dim3(64 * wv_src), (size_t)SRC_HB * (s.T + 64 * wv_src) * sizeof(float), stream,
+                        *grp, (const float*)s.q2, (long)D, (const float*)s.memkv[l], (long)2 * D, D, scale, s.att, (long)D);
+        } else
+            AVSR_LAUNCH(dec_src_attn_kernel, dim3((n + SRC_HB - 1) / SRC_HB, s.H), dim3(64 * wv_src), (size_t)SRC_HB * (s.T + 64 * wv_src) * sizeof(float), stream,
+                        (const float*)s.q2, (long)D, (const float*)s.memkv[l], (long)2 * D, D, n, s.T, scale, s.att, (long)D);
         DEC_TRY(skinny(s.att, D, w.wo2, n, D, D, w.bo2, nullptr, nullptr, 0.f, nullptr, 0, s.x1, D, s.x2, D, &s2, nullptr, stream));
         DEC_TRY(skinny(s.x2, D, w.w1, n, s.FF, D, w.b1, w.n3g, w.n3b, s.eps, &s2, 1, nullptr, 0, s.ff, s.FF, nullptr, nullptr, stream));
         DEC_TRY(skinny(s.ff, s.FF, w.w2, n, D, s.FF, w.b2, nullptr, nullptr, 0.f, nullptr, 0, s.x2, D, s.x, D, &sx, s.part, stream));
@@ -1269,6 +1423,21 @@ extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_
     DEC_TRY(skinny(x, D, s.wout, n, s.V, D, s.bout, s.ang, s.anb, s.eps, &sx, 0, nullptr, 0, s.logits, s.ldv, nullptr, nullptr, stream));
     AVSR_LAUNCH(logsoftmax_prebeam_kernel, dim3(n), dim3(SEL_NT), (size_t)(s.V + s.S) * sizeof(unsigned), stream, (const float*)s.logits, s.logp,
                 (long)s.ldv, s.V, s.S, s.cand);
+    return 0;
+}
+
+// One decoding step for the n running hypotheses (all of length L): decoder pass over the new position, pre-beam, CTC
+// prefix scores, top-K, new beam state.  host_out [K][8] f32: token, parent, total score, decoder / ctc / length-bonus
+// sums, language-model sum (0 without one), 0 -- valid on return (the call synchronises the stream).  Returns K through n_out.
+// With a language model attached its pass is issued first, in line on the same stream (DESIGN.md section 7).
+extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
+    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(s.U == 0, "beam_step: the session runs a group of utterances (avsr_beam_step_batch)");
+    AVSR_REQUIRE(s.n >= 1 && s.L <= s.Lmax, "beam_step: no running hypotheses / maximum length reached");
+    const int n = s.n, L = s.L, beam = s.beam;
+    BeamBuf& st = s.st[s.cur];
+    BeamBuf& nx = s.st[s.cur ^ 1];
+    DEC_TRY(dec_pass(s, st, n, L, beam, nullptr, stream));
     DEC_TRY(avsr_ctc_prefix_score(s.ctc_logp, s.T, s.V, s.ld_ctc, st.r, st.last, s.cand, n, s.S, L - 1, s.blank, s.r_new, s.psi,
                                   s.psi_eos, stream));
     const int NE = n * (s.S + 1);
@@ -1294,7 +1463,7 @@ extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_
 // take the hypotheses NOT listed off the beam (keep: ascending indices into the current beam)
 extern "C" int avsr_beam_keep(int64_t h, const int32_t* keep, int n_keep, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(n_keep >= 0 && n_keep <= s.n, "beam_keep: bad count");
+    AVSR_REQUIRE(s.U == 0 && n_keep >= 0 && n_keep <= s.n, "beam_keep: bad count");
     if (n_keep == s.n) return 0;
     if (n_keep > 0) {
         IdxList il;
@@ -1318,6 +1487,187 @@ extern "C" int avsr_beam_fetch_yseq(int64_t h, int64_t* host_yseq, int* ldy_out,
     const int e = avsr_copy_to_host_sync(host_yseq, s.st[s.cur].yseq, (size_t)s.n * s.ldy * sizeof(int64_t), stream);
     if (e != 0) {
         avsr_set_error2("beam_fetch_yseq", hipGetErrorString((hipError_t)e));
+        return 2;
+    }
+    *ldy_out = s.ldy;
+    *L_out = s.L;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A GROUP of utterances through the same steps (batch_beam_search.py:208-349 once per utterance in the reference: the searches are
+// independent, a label-synchronous step serves them together).  The running hypotheses of all utterances are one packed row list --
+// utterance u owns rows [off[u], off[u] + n[u]) -- at the same position L (they start together), so embedding, linear layers,
+// self-attention (cache pitch U * beam, ancestry = packed row of the ancestor at that step), pre-beam and the language model's pass
+// run on the packed rows as they are, n = all rows; source attention, CTC prefix scores, the selection (one block per utterance,
+// K = beam each) and the state update take the per-utterance row range / length / regions from a descriptor.  A row's arithmetic
+// does not depend on what else is in the group.
+static bool group_sizes(const Session& s, int U, const int32_t* T, size_t& frames, int& Tmax) {
+    if (U < 1 || U > MAX_UTT || U * s.beam > MAX_ROWS) return false;
+    frames = 0;
+    Tmax = 0;
+    for (int u = 0; u < U; u++) {
+        if (T[u] < 1) return false;
+        frames += (size_t)T[u];
+        Tmax = T[u] > Tmax ? T[u] : Tmax;
+    }
+    return true;
+}
+
+// 0 (and the error text) for a group the session does not take: more than 32 utterances or more than 1024 rows (U * beam)
+extern "C" int64_t avsr_beam_batch_workspace_bytes(int64_t h, int U, const int32_t* T, int Lmax) {
+    Session tmp = *reinterpret_cast<Session*>((intptr_t)h);
+    size_t frames;
+    int Tmax;
+    if (!group_sizes(tmp, U, T, frames, Tmax) || Lmax < 1) {
+        avsr_set_error("beam_batch_workspace_bytes: bad group (1 <= U <= 32, U * beam <= 1024, T >= 1)");
+        return 0;
+    }
+    Carver c{nullptr};
+    carve(tmp, c, (size_t)U * tmp.beam, frames, Lmax);
+    return (int64_t)c.off + 256;
+}
+
+// New group: per utterance what avsr_beam_begin takes (arrays of length U in host memory), ONE workspace of
+// avsr_beam_batch_workspace_bytes(handle, U, T, Lmax), Lmax = the most steps any of them takes.
+extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memory, const int32_t* T, const float* const* ctc_logp,
+                                     const int32_t* ld_ctc, const float* const* r_init, void* ws, int64_t ws_bytes, int Lmax, hipStream_t stream) {
+    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
+    size_t frames;
+    int Tmax;
+    AVSR_REQUIRE(group_sizes(s, U, T, frames, Tmax), "beam_begin_batch: group too large or empty (1 <= U <= 32, U * beam <= 1024 rows, T >= 1)");
+    AVSR_REQUIRE(Lmax >= 1 && Lmax + 1 <= s.pe_rows, "beam_begin_batch: bad lengths (position table too short?)");
+    AVSR_REQUIRE(!s.lm.on || Lmax + 1 <= s.lm.pe_rows, "beam_begin_batch: the language model's position table is too short");
+    Carver c{reinterpret_cast<char*>(ws)};
+    carve(s, c, (size_t)U * s.beam, frames, Lmax);
+    AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin_batch: workspace too small");
+    s.U = U;
+    s.T = s.Tmax = Tmax;
+    s.Lmax = Lmax;
+    s.n = U;
+    s.L = 1;
+    s.cur = 0;
+    long f0 = 0;
+    PtrList ri;
+    int ones[MAX_UTT];
+    for (int u = 0; u < MAX_UTT; u++) {
+        ri.p[u] = u < U ? r_init[u] : nullptr;
+        ones[u] = 1;
+        if (u >= U) continue;
+        s.utt[u] = Utt{u, 1, u, 1, T[u], 0, f0};
+        s.u_logp[u] = ctc_logp[u];
+        s.u_ld[u] = ld_ctc[u];
+        for (int l = 0; l < s.nl; l++)
+            DEC_TRY(gemm(memory[u], s.D, s.layers[l].wkv2, T[u], 2 * s.D, s.D, s.layers[l].bkv2, 0, nullptr, 0, s.memkv[l] + (size_t)f0 * 2 * s.D,
+                         2 * s.D, stream));
+        f0 += T[u];
+    }
+    const Group g = group_of(s, ones);
+    AVSR_LAUNCH(beam_init_group_kernel, dim3((2 * Tmax + 255) / 256, U), dim3(256), 0, stream, s.st[0], g, ri, s.ldy, U * s.beam, s.beam, s.sos);
+    AVSR_CHECK_LAUNCH("beam_begin_batch");
+    return 0;
+}
+
+// ONE step for all running hypotheses of all running utterances: the launches of avsr_beam_step on the packed rows, one
+// device-to-host copy of [rows][8] records (utterance after utterance, the columns of avsr_beam_step; `parent` counts within the
+// utterance), one stream synchronise.  n_out [U]: records per utterance (beam; 0 for a retired one).
+extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
+    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(s.U >= 1, "beam_step_batch: no group (avsr_beam_begin_batch)");
+    const int U = s.U, L = s.L, beam = s.beam, pitch = U * beam;
+    int nn[MAX_UTT], off[MAX_UTT], cnt[MAX_UTT], Ts[MAX_UTT];
+    int64_t f0[MAX_UTT];
+    for (int u = 0; u < U; u++) nn[u] = s.utt[u].n > 0 ? beam : 0;
+    const Group g = group_of(s, nn);
+    const int n = g.rows;
+    AVSR_REQUIRE(n >= 1 && L <= s.Lmax, "beam_step_batch: no running hypotheses / maximum length reached");
+    int K = 0, n_max = 0;
+    for (int u = 0; u < U; u++) {
+        off[u] = g.u[u].off;
+        cnt[u] = g.u[u].n;
+        Ts[u] = g.u[u].T;
+        f0[u] = g.u[u].f0;
+        K += nn[u];
+        n_max = cnt[u] > n_max ? cnt[u] : n_max;
+    }
+    BeamBuf& st = s.st[s.cur];
+    BeamBuf& nx = s.st[s.cur ^ 1];
+    DEC_TRY(dec_pass(s, st, n, L, pitch, &g, stream));
+    DEC_TRY(avsr_ctc_prefix_score_batch(U, s.u_logp, Ts, s.u_ld, s.V, st.r, st.last, s.cand, off, cnt, f0, beam, s.S, L - 1, s.blank, s.r_new,
+                                        s.psi, s.psi_eos, stream));
+    SelectArgs a{s.logp, (long)s.ldv, s.cand, s.psi, s.psi_eos, st.sc + 4 * pitch, st.sc, 0, s.S, beam, s.eos, s.blank, s.has_len,
+                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv};
+    AVSR_LAUNCH(beam_select_group_kernel, dim3(U), dim3(SEL_NT), (size_t)(2 * n_max * (s.S + 1) + beam + n_max * s.S + n_max) * 4, stream, a, g);
+    AVSR_LAUNCH(beam_update_group_kernel, dim3(K), dim3(256), 0, stream, st, nx, g, s.ldy, pitch, beam, L, s.S, (const int*)s.sel,
+                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, s.host_dev);
+    AVSR_CHECK_LAUNCH("beam_step_batch");
+    const int e = avsr_copy_to_host_sync(host_out, s.host_dev, (size_t)K * 8 * sizeof(float), stream);
+    if (e != 0) {
+        avsr_set_error2("beam_step_batch", hipGetErrorString((hipError_t)e));
+        return 2;
+    }
+    s.cur ^= 1;
+    s.L = L + 1;
+    int o = 0;
+    for (int u = 0; u < U; u++) {
+        // (`parent` of a record is a packed row of the previous beam: the host sees it within the utterance, as avsr_beam_step gives it)
+        for (int k = 0; k < nn[u]; k++) host_out[(size_t)(o + k) * 8 + 1] -= (float)off[u];
+        s.utt[u].n = nn[u];
+        s.utt[u].off = o;
+        o += nn[u];
+        n_out[u] = nn[u];
+    }
+    s.n = K;
+    return 0;
+}
+
+// Take hypotheses off the beams: keep = for utterance after utterance the ascending indices WITHIN that utterance's current beam
+// that survive, n_keep [U] how many per utterance; n_keep[u] == 0 retires utterance u (it takes no further part in the steps).
+extern "C" int avsr_beam_keep_batch(int64_t h, const int32_t* keep, const int32_t* n_keep, hipStream_t stream) {
+    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(s.U >= 1, "beam_keep_batch: no group (avsr_beam_begin_batch)");
+    int nn[MAX_UTT];
+    bool same = true;
+    int total = 0;
+    for (int u = 0; u < s.U; u++) {
+        AVSR_REQUIRE(n_keep[u] >= 0 && n_keep[u] <= s.utt[u].n, "beam_keep_batch: bad count");
+        nn[u] = n_keep[u];
+        same = same && n_keep[u] == s.utt[u].n;
+        total += n_keep[u];
+    }
+    if (same) return 0;
+    if (total > 0) {
+        const Group g = group_of(s, nn);
+        RowList rl;
+        int k = 0;
+        for (int u = 0; u < s.U; u++)
+            for (int i = 0; i < nn[u]; i++, k++) {
+                AVSR_REQUIRE(keep[k] >= 0 && keep[k] < g.u[u].n, "beam_keep_batch: index out of range");
+                rl.from[k] = (unsigned short)(g.u[u].off + keep[k]);
+            }
+        for (; k < MAX_ROWS; k++) rl.from[k] = 0;
+        AVSR_LAUNCH(beam_keep_group_kernel, dim3(total), dim3(256), 0, stream, s.st[s.cur], s.st[s.cur ^ 1], g, s.ldy, s.U * s.beam, s.beam, s.L, rl);
+        AVSR_CHECK_LAUNCH("beam_keep_batch");
+        s.cur ^= 1;
+    }
+    int o = 0;
+    for (int u = 0; u < s.U; u++) {
+        s.utt[u].n = nn[u];
+        s.utt[u].off = o;
+        o += nn[u];
+    }
+    s.n = total;
+    return 0;
+}
+
+// token sequences of all current beams: host_yseq [rows][ldy] int64, utterance after utterance (n of the last step / keep each), the
+// first L entries of every row valid (synchronises)
+extern "C" int avsr_beam_fetch_yseq_batch(int64_t h, int64_t* host_yseq, int* ldy_out, int* L_out, hipStream_t stream) {
+    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(s.U >= 1, "beam_fetch_yseq_batch: no group (avsr_beam_begin_batch)");
+    const int e = avsr_copy_to_host_sync(host_yseq, s.st[s.cur].yseq, (size_t)s.n * s.ldy * sizeof(int64_t), stream);
+    if (e != 0) {
+        avsr_set_error2("beam_fetch_yseq_batch", hipGetErrorString((hipError_t)e));
         return 2;
     }
     *ldy_out = s.ldy;

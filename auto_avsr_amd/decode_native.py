@@ -18,6 +18,16 @@ import torch
 from . import _lib, ops
 
 MAX_BEAM = 128
+MAX_GROUP, MAX_GROUP_ROWS = 32, 1024  # csrc/decode.hip: utterances of a group, packed rows (U * beam) of a group
+
+
+def search_maxlen(T, maxlenratio):
+    """Steps a search of a T-frame utterance takes at the most (beam_search.py:349-354)."""
+    if maxlenratio == 0:
+        return T
+    if maxlenratio < 0:
+        return -1 * int(maxlenratio)
+    return max(1, int(maxlenratio * T))
 
 
 def skinny_len_ok(K, sliced_ok):
@@ -258,6 +268,116 @@ class NativeBeam:
             return [] if minlenratio < 0.1 else self.search(x, maxlenratio, max(0.0, minlenratio - 0.1), ctc_state=(logp, r_init))
         return nbest
 
+    # ------------------------------------------------------------------------------------------------ a group of utterances
+    def group_workspace_bytes(self, Ts, Lmax):
+        """Bytes `search_group` allocates for utterances of Ts frames and at most Lmax steps (after `_bind`)."""
+        arr = (ctypes.c_int32 * len(Ts))(*Ts)
+        n = _lib.lib().call("avsr_beam_batch_workspace_bytes", self.handle, len(Ts), ctypes.cast(arr, ctypes.c_void_p), Lmax)
+        if n <= 0:
+            raise _lib.AvsrLibraryError("avsr_beam_batch_workspace_bytes: " + _lib.lib().cdll.avsr_last_error().decode())
+        return n
+
+    @torch.no_grad()
+    def search_group(self, xs, pre, maxlenratio=0.0, minlenratio=0.0):
+        """The searches of `search` for U utterances with ONE library call per step (avsr_beam_step_batch): every utterance has its
+        own maxlen, takes its forced end there, collects its own <eos> hypotheses, stops by its own end detection, and is retired
+        (n_keep = 0) while the others go on.  pre[u] = prepare_ctc of xs[u].  Returns one n-best list per utterance."""
+        from .decoding import Hypothesis
+
+        bs = self.bs
+        U, dev = len(xs), xs[0].device
+        Ts = [int(x.shape[0]) for x in xs]
+        maxlens = [search_maxlen(T, maxlenratio) for T in Ts]
+        Lmax = max(maxlens)
+        self._bind(dev, Lmax + 2)
+        L = _lib.lib()
+        mems = [_f32(x) for x in xs]
+        nws = self.group_workspace_bytes(Ts, Lmax)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        stream = ops._stream(mems[0])
+        i32, ptr = ctypes.c_int32 * U, ctypes.c_void_p * U
+        vp = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+        L.call("avsr_beam_begin_batch", self.handle, U, vp(ptr(*[m.data_ptr() for m in mems])), vp(i32(*Ts)),
+               vp(ptr(*[p[0].data_ptr() for p in pre])), vp(i32(*[p[0].stride(0) for p in pre])), vp(ptr(*[p[1].data_ptr() for p in pre])),
+               ws.data_ptr(), nws, Lmax, stream)
+        rows = U * bs.beam_size
+        pin = dev.type == "cuda"
+        host = getattr(self, "group_host", None)
+        if host is None or host.shape[0] < rows * 8:
+            host = self.group_host = torch.empty(rows * 8, dtype=torch.float32, pin_memory=pin)
+        host_np = host.numpy().reshape(-1, 8)
+        yseq_host = getattr(self, "group_yseq_host", None)
+        if yseq_host is None or yseq_host.shape[0] < rows * (Lmax + 2):
+            yseq_host = self.group_yseq_host = torch.empty(rows * (Lmax + 2), dtype=torch.int64, pin_memory=pin)
+        n_out = i32()
+        names = ["decoder"] + [k for k in ("lm", "length_bonus") if k in bs.full_scorers] + ["ctc"]
+        col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6}
+        eos = bs.eos
+        ended = [[] for _ in range(U)]
+        best = [-math.inf] * U
+        best_len = [{} for _ in range(U)]
+        running = [True] * U
+
+        def end(u, row, ys, forced):
+            ys = list(ys) + ([eos] if forced else [])
+            sc = float(row[2])
+            ended[u].append(Hypothesis(yseq=torch.tensor(ys, dtype=torch.int64), score=sc, scores={k: float(row[col[k]]) for k in names},
+                                       states={}))
+            best[u] = max(best[u], sc)
+            best_len[u][len(ys)] = max(best_len[u].get(len(ys), -math.inf), sc)
+
+        for i in range(Lmax):
+            L.call("avsr_beam_step_batch", self.handle, host.data_ptr(), vp(n_out), stream)
+            counts = list(n_out)
+            fetched = None
+
+            def fetch():
+                ldy, Lc = ctypes.c_int(0), ctypes.c_int(0)
+                L.call("avsr_beam_fetch_yseq_batch", self.handle, yseq_host.data_ptr(), vp(ctypes.pointer(ldy)), vp(ctypes.pointer(Lc)), stream)
+                return yseq_host.numpy(), ldy.value, Lc.value
+
+            keep, n_keep, changed, off = [], [0] * U, False, 0
+            for u in range(U):
+                K = counts[u]
+                if not running[u]:
+                    continue
+                out = host_np[off: off + K]
+                tok = out[:, 0].astype(np.int64)
+                if i == maxlens[u] - 1:  # this utterance's forced end (beam_search.py:430-436)
+                    fetched = fetched or fetch()
+                    ys, ldy, Lc = fetched
+                    for b in range(K):
+                        end(u, out[b], ys[(off + b) * ldy: (off + b) * ldy + Lc], True)
+                    alive = []
+                else:
+                    is_eos = tok == eos
+                    alive = list(range(K))
+                    if is_eos.any():
+                        fetched = fetched or fetch()
+                        ys, ldy, Lc = fetched
+                        for b in np.nonzero(is_eos)[0].tolist():
+                            end(u, out[b], ys[(off + b) * ldy: (off + b) * ldy + Lc], False)
+                        alive = np.nonzero(~is_eos)[0].tolist()
+                if maxlenratio == 0.0 and ended[u] and self._end_detect(best[u], best_len[u], i):
+                    alive = []
+                if not alive:
+                    running[u] = False
+                changed = changed or len(alive) != K
+                keep += alive
+                n_keep[u] = len(alive)
+                off += K
+            if not any(running):
+                break
+            if changed:
+                L.call("avsr_beam_keep_batch", self.handle, vp((ctypes.c_int32 * max(1, len(keep)))(*keep)), vp(i32(*n_keep)), stream)
+        results = []
+        for u in range(U):
+            nbest = sorted(ended[u], key=lambda h: float(h.score), reverse=True)
+            if not nbest and minlenratio >= 0.1:  # (beam_search.py:448-456: the retry is a search of its own)
+                nbest = self.search(xs[u], maxlenratio, max(0.0, minlenratio - 0.1), ctc_state=pre[u])
+            results.append(nbest)
+        return results
+
     @staticmethod
     def _end_detect(best, best_len, i, M=3, D_end=math.log(1 * math.exp(-10))):
         """decoding.end_detect (e2e_asr_common.py:17-47) on the running maxima instead of the list of dicts."""
@@ -325,4 +445,47 @@ def search_many(bs, xs, workers=4, maxlenratio=0.0, minlenratio=0.0):
             torch.cuda.current_stream(dev).wait_stream(st)
     if errors:
         raise errors[0]
+    return results
+
+
+def search_batch(bs, xs, max_batch=8, max_workspace_bytes=8 << 30, maxlenratio=0.0, minlenratio=0.0):
+    """Beam searches of several utterances with ONE decoding step per GROUP of utterances (avsr_beam_step_batch): the U x beam running
+    hypotheses of a group go through the same ~60 launches, every weight is read once per step instead of once per step and
+    utterance.  Returns [bs(x) for x in xs] in input order (a row's arithmetic does not depend on what else is in its group).
+
+    Utterances are sorted by length and cut into consecutive groups of at most `max_batch` (and at most 32 utterances / 1024
+    packed rows, the library's limits); a group takes as many steps as its longest member.  A group is shrunk, never below one
+    utterance, until its workspace fits `max_workspace_bytes`.  The workspace of a group (avsr_beam_batch_workspace_bytes) is, with
+    R = U * beam rows, F = the frames of all its utterances, D / FF / V the decoder's widths and S the pre-beam size, in bytes
+        layers * (Lmax * R * 3 D + F * 2 D) * 4              self-attention caches [Lmax][R][3 D], memory K / V [F][2 D]
+      + 2 * (R * (Lmax + 2) * 12 + 2 * F * beam * 4)         two beam states: tokens, ancestry, CTC state [F][2][beam]
+      + 2 * F * beam * S * 4                                 CTC forward variables of every candidate
+      + R * (14 D + FF + 2 V + 3 S) * 4                      activations, K-slice partial sums, logits, log-probabilities, candidates
+    plus, with a language model of width D' / FF' and `lm_layers` layers,
+        lm_layers * Lmax * R * 3 D' * 4 + R * (11 D' + FF' + 2 V) * 4.
+    (per-row scalars and the 256-byte alignment of every table left out).  The cache term dominates: 1.18 GB per layer for U = 8, beam 40, D = 768, Lmax = 400."""
+    xs = list(xs)
+    if not xs:
+        return []
+    dev = xs[0].device
+    ctc = bs.part_scorers["ctc"]
+    sess = bs._native
+    maxpos = max(search_maxlen(int(x.shape[0]), maxlenratio) for x in xs) + 2
+    sess._bind(dev, maxpos)
+    cap = max(1, min(int(max_batch), MAX_GROUP, MAX_GROUP_ROWS // bs.beam_size))
+    order = sorted(range(len(xs)), key=lambda i: int(xs[i].shape[0]))
+    results = [None] * len(xs)
+    at = 0
+    while at < len(order):
+        idx = order[at: at + cap]
+        while len(idx) > 1:
+            Ts = [int(xs[i].shape[0]) for i in idx]
+            if sess.group_workspace_bytes(Ts, max(search_maxlen(T, maxlenratio) for T in Ts)) <= max_workspace_bytes:
+                break
+            idx = idx[:-1]
+        group = [xs[i] for i in idx]
+        pre = [prepare_ctc(ctc, x) for x in group]
+        for i, nbest in zip(idx, sess.search_group(group, pre, maxlenratio, minlenratio)):
+            results[i] = nbest
+        at += len(idx)
     return results

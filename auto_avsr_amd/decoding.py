@@ -300,6 +300,22 @@ class BatchBeamSearch(torch.nn.Module):
                 return search_many(self, list(xs), workers, maxlenratio, minlenratio)
         return [self(x, maxlenratio, minlenratio) for x in xs]
 
+    def forward_batch(self, xs, batch: int = 8, max_workspace_bytes: int = 8 << 30, maxlenratio: float = 0.0, minlenratio: float = 0.0):
+        """Not in the reference: the searches of several utterances (encoder outputs (T_i, D)) share their decoding steps -- groups of
+        at most `batch` utterances of similar length go through ONE library call per step (decode_native.search_batch; the
+        workspace formula is there).  Returns [self(x) for x in xs]; scorer sets the library does not cover are searched one after
+        the other by the python step."""
+        if NATIVE_BEAM and self._native is not False:
+            if self._native is None:
+                from .decode_native import NativeBeam
+
+                self._native = NativeBeam(self) if NativeBeam.supported(self) else False
+            if self._native:
+                from .decode_native import search_batch
+
+                return search_batch(self, list(xs), batch, max_workspace_bytes, maxlenratio, minlenratio)
+        return [self(x, maxlenratio, minlenratio) for x in xs]
+
     def _keep_state(self, k, st, keep):
         if st is None:
             return None

@@ -29,6 +29,10 @@ def parse_args(argv=None):
     p.add_argument("--decode-workers", type=int, default=1,
                    help="beam searches in flight at once (host threads + streams, one decoding session each); 1 = the reference's "
                         "one-utterance-at-a-time loop")
+    p.add_argument("--decode-batch", type=int, default=0, metavar="N",
+                   help="decode groups of up to N utterances of similar length with ONE decoding step per group (the batched native "
+                        "beam search; utterances are taken in windows of 4 N); 0 = off.  Not with --decode-workers > 1 or "
+                        "--decode-mode rescore")
     p.add_argument("--timestamps", type=str, default=None, metavar="PATH",
                    help="write one JSON line per utterance with the word timestamps of its hypothesis (CTC forced alignment on the "
                         "device, 40 ms per encoder frame): {utt, hyp, score, words: [{word, start, end}] or null}")
@@ -42,12 +46,21 @@ def parse_args(argv=None):
                         "decoding -- a CTC prefix beam search on the device, then one teacher-forced decoder (+ LM) pass over its n-best")
     p.add_argument("--rescore-beam", type=int, default=16, help="--decode-mode rescore: beam (and n-best) of the first pass, 2 .. 64")
     p.add_argument("--rescore-topk", type=int, default=16, help="--decode-mode rescore: non-blank tokens considered per frame, 1 .. 32")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.decode_batch < 0:
+        p.error("--decode-batch must be >= 0")
+    if args.decode_batch > 1 and args.decode_workers > 1:
+        p.error("--decode-batch and --decode-workers > 1 are two ways of decoding several utterances at once: choose one")
+    if args.decode_batch > 1 and args.decode_mode == "rescore":
+        p.error("--decode-batch groups the steps of the label-synchronous search: it does not apply to --decode-mode rescore")
+    return args
 
 
-def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps=None):
+def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps=None, decode_batch=0):
     """Trainer.test without Lightning: the module's own hooks over the loader (lightning.py:69-84,116-123).  decode_workers > 1:
     utterances are taken in groups whose beam searches run concurrently (ModelModule.decode_many); same transcripts, same WER.
+    decode_batch > 1: utterances are taken in windows of 4 * decode_batch whose searches share their decoding steps in groups of
+    at most decode_batch utterances of similar length; same transcripts, same WER.
     timestamps: path of a JSON-lines file that receives, per utterance, the word timestamps of its hypothesis (CTC forced
     alignment on the encoder output the decoding already computed); without it nothing is aligned."""
     import json
@@ -60,7 +73,7 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps
     records = [] if timestamps else None
     module.timestamp_records = records  # test_step appends to it
     with torch.no_grad():
-        if decode_workers <= 1:
+        if decode_workers <= 1 and decode_batch <= 1:
             for i, sample in enumerate(loader):
                 sample = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in sample.items()}
                 module.test_step(sample, i)
@@ -71,7 +84,8 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps
 
             def flush():
                 nonlocal done
-                for s, predicted in zip(group, module.decode_many([s["input"] for s in group], workers=decode_workers, records=records)):
+                for s, predicted in zip(group, module.decode_many([s["input"] for s in group], workers=decode_workers, records=records,
+                                                                   batch=decode_batch)):
                     actual = module.text_transform.post_process(s["target"])
                     module.total_edit_distance += compute_word_level_distance(actual, predicted)
                     module.total_length += len(actual.split())
@@ -82,7 +96,7 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps
 
             for sample in loader:
                 group.append({k: (v.to(device) if torch.is_tensor(v) else v) for k, v in sample.items()})
-                if len(group) == 4 * decode_workers:
+                if len(group) == 4 * (decode_batch if decode_batch > 1 else decode_workers):
                     flush()
             if group:
                 flush()
@@ -128,6 +142,7 @@ def cli_main(argv=None):
     else:
         loader = datamodule.test_dataloader()
     wer = run_test_loop(module, loader, torch.device("cuda"), decode_workers=args.decode_workers, timestamps=args.timestamps,
+                        decode_batch=args.decode_batch,
                         log=lambda i, d, n: logging.info(f"utt {i}: running WER {d / max(n, 1):.4f} ({d}/{n} words)"))
     print(f"WER {wer:.4f} over {module.total_length} reference words")
     return wer

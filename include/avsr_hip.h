@@ -520,6 +520,15 @@ int avsr_conv3x3_wgrad_bf16(const void* dy, const void* x, float* dwp, const voi
 int avsr_ctc_prefix_score(const float* logp, int T, int V, int ldv, const float* r_prev, const int64_t* last,
                           const int64_t* cand, int NH, int S, int out_len, int blank, float* r_new, float* psi,
                           float* psi_eos, avsr_stream_t stream);
+/* the same for a group of U <= 32 utterances whose running hypotheses are one packed row list at the same prefix length (one call of
+ * CTCPrefixScoreTH.__call__ per utterance in the reference): utterance u owns rows [row_off[u], row_off[u] + n_rows[u]) of last /
+ * cand [rows][S] / psi [rows][S] / psi_eos [rows], its own logp[u] [T[u]][ldv[u]]; with F = frame_off[u] (frames of the utterances
+ * before it) its state is r_prev + 2 F pitch laid out [T[u]][2][n_rows[u]], its output r_new + 2 F pitch S laid out
+ * [T[u]][2][n_rows[u]][S]; n_rows[u] == 0 skips it.  Arrays of length U are host memory. */
+int avsr_ctc_prefix_score_batch(int U, const float* const* logp, const int32_t* T, const int32_t* ldv, int V, const float* r_prev,
+                                const int64_t* last, const int64_t* cand, const int32_t* row_off, const int32_t* n_rows,
+                                const int64_t* frame_off, int pitch, int S, int out_len, int blank, float* r_new, float* psi,
+                                float* psi_eos, avsr_stream_t stream);
 
 /* ---- beam search, one decoding step per host call (decode.hip) ------------------------------------------------------
  * One iteration of BatchBeamSearch.search (espnet/nets/batch_beam_search.py:208-349 over beam_search.py:330-406) with the
@@ -569,6 +578,29 @@ int avsr_beam_step(int64_t handle, float* host_out, int* n_out, avsr_stream_t st
 int avsr_beam_keep(int64_t handle, const int32_t* keep, int n_keep, avsr_stream_t stream);
 /* token sequences of the current beam into host_yseq [n][*ldy_out] (first *L_out entries of a row valid); synchronises */
 int avsr_beam_fetch_yseq(int64_t handle, int64_t* host_yseq, int* ldy_out, int* L_out, avsr_stream_t stream);
+/* ---- the same search for a GROUP of utterances per step (the reference runs batch_beam_search.py:208-349 once per utterance; the
+ * searches are independent, so one label-synchronous step can serve U of them).  Same handle, bound weights and language model as
+ * above.  The running hypotheses of all utterances form one packed row list, utterance after utterance, all at the same position;
+ * 1 <= U <= 32 and U * beam <= 1024 rows, larger groups are refused.  A session runs either one utterance or one group at a time.
+ * Arrays of length U are host memory. */
+/* workspace of a group with frame counts T[U] and at most Lmax steps (0 and avsr_last_error for a group that is refused): the
+ * tables of avsr_beam_workspace_bytes sized for U * beam rows (per layer a [Lmax][U * beam][3 D] cache, the language model's too) and
+ * for the frames of all utterances (memory K / V, CTC state and r_new regions behind one another) */
+int64_t avsr_beam_batch_workspace_bytes(int64_t handle, int U, const int32_t* T, int Lmax);
+/* avsr_beam_begin for every utterance u: memory[u] [T[u]][D], ctc_logp[u] [T[u]][ld_ctc[u]], r_init[u] [T[u]][2]; projects every
+ * memory's K / V, resets every beam to <sos>; Lmax = the most steps any of them takes */
+int avsr_beam_begin_batch(int64_t handle, int U, const float* const* memory, const int32_t* T, const float* const* ctc_logp,
+                          const int32_t* ld_ctc, const float* const* r_init, void* workspace, int64_t workspace_bytes, int Lmax,
+                          avsr_stream_t stream);
+/* one step (beam_search.py:330-406) for all running hypotheses of all running utterances: the launches of avsr_beam_step on the packed
+ * rows, ONE device-to-host copy of [rows][8] records (the columns of avsr_beam_step, utterance after utterance, parent counted within
+ * the utterance), ONE stream synchronise; n_out [U]: records of every utterance (0: retired) */
+int avsr_beam_step_batch(int64_t handle, float* host_out, int* n_out, avsr_stream_t stream);
+/* drop hypotheses (batch_beam_search.py:178-206 per utterance): keep = utterance after utterance the ascending indices within that
+ * utterance's beam that stay, n_keep [U] their counts; n_keep[u] == 0 retires utterance u (beam_search.py:430-446: its search is over) */
+int avsr_beam_keep_batch(int64_t handle, const int32_t* keep, const int32_t* n_keep, avsr_stream_t stream);
+/* token sequences of all beams into host_yseq [rows][*ldy_out], utterance after utterance (first *L_out entries of a row valid); synchronises */
+int avsr_beam_fetch_yseq_batch(int64_t handle, int64_t* host_yseq, int* ldy_out, int* L_out, avsr_stream_t stream);
 
 /* ---- optimizer step (optim.hip): global-norm clip + AdamW + warm-up cosine schedule, all parameters in 3 launches ---
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW(...).step() +

@@ -222,17 +222,19 @@ class ModelModule(_Base):
         words, score = self.align_encoded(enc_feat, token_ids)
         return {"hyp": text, "score": score, "words": words}
 
-    def decode_many(self, samples, workers=4, records=None):
+    def decode_many(self, samples, workers=4, records=None, batch=0):
         """Not in the reference: the transcripts of several utterances, their beam searches running concurrently (one host
-        thread + stream + decoding session per worker, BatchBeamSearch.forward_many); front-end / encoder one utterance at a
-        time as in `_decode`.  records: a list that receives one word-timestamp record per utterance (eval.py --timestamps)."""
+        thread + stream + decoding session per worker, BatchBeamSearch.forward_many) or, with batch > 1, sharing their decoding
+        steps in groups of at most `batch` utterances (BatchBeamSearch.forward_batch); front-end / encoder one utterance at a
+        time, unpadded, as in `_decode`.  records: a list that receives one word-timestamp record per utterance (eval.py --timestamps)."""
         encs = []
         for sample in samples:
             x = self.model.proj_encoder(self.model.frontend(sample.unsqueeze(0)))
             enc_feat, _ = self.model.encoder(x, None)
             encs.append(enc_feat.squeeze(0))
         out = []
-        for enc, nbest in zip(encs, self.beam_search.forward_many(encs, workers=workers)):
+        nbests = self.beam_search.forward_batch(encs, batch=batch) if batch > 1 else self.beam_search.forward_many(encs, workers=workers)
+        for enc, nbest in zip(encs, nbests):
             ids = torch.tensor(list(map(int, nbest[0].asdict()["yseq"][1:])))
             out.append(self.text_transform.post_process(ids).replace("<eos>", ""))
             if records is not None:

@@ -35,6 +35,10 @@ def main():
                          "the reference's best hypothesis in the n-best, share of utterances whose winner scores at least the reference's")
     ap.add_argument("--two-pass-once", type=int, default=0, metavar="T",
                     help="one warm-up and one two-pass decode of a T-frame utterance and nothing else (the program of a kernel-trace run)")
+    ap.add_argument("--batch", action="store_true",
+                    help="batched native search rows instead of the default ones: 16 utterances of T = 100 and of T = 400 frames through "
+                         "BatchBeamSearch.forward_batch in groups of 1, 4, 8 and 16 beside one search at a time and forward_many(workers=4), "
+                         "alternated, on the same encoder outputs (precise mode; python tools/bench_decode.py --batch > profiles/batch_decode.json)")
     ap.add_argument("--rescore-beam", type=int, default=16)
     ap.add_argument("--rescore-topk", type=int, default=16)
     ap.add_argument("--modes", type=str, default="precise", help="--two-pass: comma-separated numerical modes (eval.py decodes in precise)")
@@ -43,6 +47,8 @@ def main():
         return main_lm(args)
     if args.two_pass_sweep:
         return main_two_pass_sweep(args)
+    if args.batch:
+        return main_batch(args)
     if args.two_pass or args.two_pass_once:
         return main_two_pass(args)
     import lightning
@@ -340,6 +346,73 @@ def main_two_pass(args):
     AF.set_mode("bf16")
     print(json.dumps({"metric": "two-pass decoding (CTC prefix beam search on the device + teacher-forced rescoring) against the native one-call "
                                 "hybrid search, video E2E 250M, vocabulary 5049, search only (encoder output ready)",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def main_batch(args):
+    import statistics
+
+    import lightning
+    from synth import synth_batch, synth_state_dict
+
+    from auto_avsr_amd import decoding
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode.py --batch needs an MI355X: there is nothing to time without one")
+    dev = torch.device("cuda:0")
+    m = E2E(5049, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    bs = lightning.get_beam_search_decoder(m, [str(i) for i in range(5049)], beam_size=args.beam)
+    decoding.NATIVE_BEAM = True
+    AF.set_mode("precise")
+    N, groups, big = 16, (1, 4, 8, 16), 64 << 30
+    rows = []
+    for T in (100, 400):
+        encs = []
+        with torch.no_grad():
+            for i in range(N):
+                x, _, _ = synth_batch("video", 1, T, 3, 5049, seed=T if i == 0 else 1000 + i, lengths=[T])
+                encs.append(m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float())
+        sides = {"one_at_a_time": lambda: [bs(e) for e in encs], "forward_many_workers_4": lambda: bs.forward_many(encs, workers=4)}
+        for U in groups:
+            sides[f"forward_batch_{U}"] = lambda U=U: bs.forward_batch(encs, batch=U, max_workspace_bytes=big)
+        # before anything is timed (this is also every side's warm-up): the batched best hypotheses are the one-at-a-time ones
+        with torch.no_grad():
+            warm = {k: f() for k, f in sides.items()}
+        torch.cuda.synchronize()
+        assert bs._native
+        best = [nb[0].asdict()["yseq"] for nb in warm["one_at_a_time"]]
+        for k, res in warm.items():
+            assert [nb[0].asdict()["yseq"] for nb in res] == best, f"{k}: best hypotheses differ from the one-at-a-time search (T = {T})"
+        ts = {k: [] for k in sides}
+        for _ in range(args.reps):  # the sides alternate within a repetition
+            for k, f in sides.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                with torch.no_grad():
+                    f()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        steps = max(len(y) for y in best) - 1
+        Ts = [T] * N
+        row = {"T_frames": T, "utterances": N, "beam": args.beam, "mode": "precise", "longest_best_hypothesis_tokens": steps, "sides": {}}
+        for k, v in ts.items():
+            med = statistics.median(v)
+            row["sides"][k] = {"ms_total": {"median": round(med, 2), "min": round(min(v), 2), "max": round(max(v), 2)},
+                               "utterances_per_sec": {"median": round(N / (med / 1e3), 2), "min": round(N / (max(v) / 1e3), 2),
+                                                      "max": round(N / (min(v) / 1e3), 2)}}
+        for U in groups:
+            row["sides"][f"forward_batch_{U}"]["workspace_bytes_per_group"] = bs._native.group_workspace_bytes(Ts[:U], T)
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        del encs, warm
+    AF.set_mode("bf16")
+    print(json.dumps({"metric": "batched native hybrid CTC / attention beam search (one decoding step per group of U utterances) beside one search "
+                                "at a time and four sessions in flight, video E2E 250M, vocabulary 5049, search only (encoder outputs ready), wall "
+                                "clock between synchronisations, one warm-up then the sides alternated",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
 
 

@@ -1,6 +1,7 @@
 """One beam search (video E2E 250M, synthetic weights, beam 40) for `rocprofv3 --kernel-trace`: the encoder runs in the bf16
-mode so that every split-plane GEMM launch in the trace belongs to the decoding steps.  python tools/prof_decode.py [T] [native] [lm]
-(lm = 1: shallow fusion with the 16 x 512 Transformer LM of tools/bench_decode.py --lm, weight 0.3)"""
+mode so that every split-plane GEMM launch in the trace belongs to the decoding steps.  python tools/prof_decode.py [T] [native] [lm] [U]
+(lm = 1: shallow fusion with the 16 x 512 Transformer LM of tools/bench_decode.py --lm, weight 0.3; U > 0: the search of U utterances of
+T frames as ONE group, BatchBeamSearch.forward_batch, in place of one utterance)"""
 import os
 import sys
 import time
@@ -15,6 +16,7 @@ def main():
     T = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     native = (sys.argv[2] if len(sys.argv) > 2 else "1") != "0"
     with_lm = (sys.argv[3] if len(sys.argv) > 3 else "0") != "0"
+    U = int(sys.argv[4]) if len(sys.argv) > 4 else 0
     import lightning
     from synth import synth_batch, synth_state_dict
 
@@ -44,10 +46,14 @@ def main():
         feats = m.proj_encoder(m.frontend(x.to(dev)))
         enc, _ = m.encoder(feats, None)
         e = enc.squeeze(0).float()
+        group = []
+        for u in range(1, U):  # further utterances of the group: other inputs, same length
+            xu, _, _ = synth_batch("video", 1, T, 3, 5049, seed=1000 + u, lengths=[T])
+            group.append(m.encoder(m.proj_encoder(m.frontend(xu.to(dev))), None)[0].squeeze(0).float())
         for rep in range(2):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            nbest = bs(e)
+            nbest = bs.forward_batch([e] + group, batch=U, max_workspace_bytes=64 << 30)[0] if U else bs(e)
             torch.cuda.synchronize()
             print(f"search {rep}: {(time.perf_counter() - t0) * 1e3:.1f} ms, {len(nbest)} hypotheses, longest {max(len(h.yseq) for h in nbest)}")
 
