@@ -176,6 +176,13 @@ AVSR_DEV void sched_fence() {
     __builtin_amdgcn_sched_barrier(0);
 #endif
 }
+// optimisation fence on one register: the compiler must assume v changed, so values derived from it are recomputed after
+// the fence instead of being kept live (loop-invariant index arithmetic that would otherwise cost registers for a whole loop)
+template <class T> AVSR_DEV void reg_opaque(T& v) {
+#ifndef AVSR_EMU
+    asm volatile("" : "+v"(v));
+#endif
+}
 template <int N> AVSR_DEV void wait_vmcnt() {
 #ifndef AVSR_EMU
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");

@@ -447,7 +447,9 @@ int avsr_comm_reduce_scatter(int slot, const void* send, void* recv, int64_t cou
  * avsr_layernorm_bwd's dx blocks (0 = 1, or 2 with a column-sum output on > 1024 rows; tools/microbench_small.py), 26 = k split of
  * avsr_gemm_h16_nt with f32 atomics onto a ZEROED f32 C (probe: tools/microbench_splitk.py; slower at M = 1600), 27 = the patch-staged
  * split-plane 3x3 kernel of conv3x3_c64_split.hip (0 = 3x3 / stride 1 / pad 1 / 64 -> 64 channel avsr_conv2d_f32s(_stats) calls on
- * pre-split operands with >= 65536 output rows; 1 = off: keep the tiled kernel; 2 = on whatever the output size).  Knobs 0..31 exist. */
+ * pre-split operands with >= 65536 output rows; 1 = off: keep the tiled kernel; 2 = on whatever the output size), 28 = 1 keeps the video-stem entry points (avsr_stem357_fwd*,
+ * avsr_stem357_wgrad) on their per-row kernels instead of the row-group kernels (groups of 4 output rows, contiguous runs of groups
+ * per persistent block; A/B arm and in-tree reference; avsr_stem357_stat_rows follows the knob).  Knobs 0..31 exist. */
 int avsr_tune(int knob, int value);
 /* bf16 implicit-GEMM convolution on the tuned LDS-DMA kernel: dgrad = 0 forward, 1 data gradient (see
  * avsr_conv2d_fwd / avsr_conv2d_dgrad for the tensor conventions); gathered channel count % 64 == 0; stride 1 or 2
@@ -482,7 +484,9 @@ int avsr_stem357_fwd_f32s(const float* x, const float* w, float* y, void* y2 /* 
                           int B, int T, int H, int W, avsr_stream_t stream);
 /* ... leaving the BatchNorm statistics of its output behind (frontend/resnet.py:203-219: Conv3d -> BatchNorm3d in batch-statistics
  * mode): row j of stats_part [stats_rows >= avsr_stem357_stat_rows(B, T, H)][2][64] = per-channel sums / sums of squares of the
- * output rows block j wrote; finish with avsr_bn_finalize_parts / avsr_bn_stats_parts */
+ * output rows block j wrote; finish with avsr_bn_finalize_parts / avsr_bn_stats_parts.  avsr_stem357_stat_rows is the block count
+ * of the launch under the current knob 28 (row-group kernel: one row per persistent block, at most 512; per-row kernel: one per
+ * 8 output rows): every row it counts is written, so the consumer sums all of them */
 int64_t avsr_stem357_stat_rows(int B, int T, int H);
 int avsr_stem357_fwd_f32s_stats(const float* x, const float* w, float* y, void* y2, void* workspace, int B, int T, int H, int W,
                                 float* stats_part, int stats_rows, avsr_stream_t stream);
