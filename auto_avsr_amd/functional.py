@@ -141,12 +141,58 @@ def _bwd_mode(fn):
     return backward
 
 
+# ---- address-keyed hand-off tables ----------------------------------------------------------------------------------
+# Autograd functions cannot see their neighbours, so they pass side information to each other under the device address of a
+# tensor both of them see.  An address names a tensor only while that tensor is alive: every entry is therefore made FROM the
+# tensors whose addresses form its key (its anchors) and holds them until it is popped or dropped, so no later allocation can
+# be answered with another tensor's entry.  The per-table checks (numel, shape, spec: views of one buffer share its address)
+# stay with the callers.
+_tables = []  # every table registers itself here: new_step() drops them all
+
+
+class _HandOff:
+    """(addresses of `anchors`) + `extra` -> (anchors, payload).  cap: at more entries than this a put() first drops the
+    table (None: the table's one writer clears it itself)."""
+
+    def __init__(self, name, cap=None):
+        self.name, self.cap, self._d = name, cap, {}
+        _tables.append(self)
+
+    @staticmethod
+    def _key(anchors, extra):
+        return tuple(a.data_ptr() for a in anchors) + tuple(extra)
+
+    def put(self, payload, *anchors, extra=(), cap=None):
+        cap = self.cap if cap is None else cap
+        if cap is not None and len(self._d) > cap:
+            self._d.clear()
+        self._d[self._key(anchors, extra)] = (anchors, payload)
+        return payload
+
+    def get(self, *anchors, extra=()):
+        """The entry (anchors, payload), or None; it stays registered."""
+        return self._d.get(self._key(anchors, extra))
+
+    def pop(self, *anchors, extra=()):
+        return self._d.pop(self._key(anchors, extra), None)
+
+    def clear(self):
+        self._d.clear()
+
+    def items(self):
+        """(key, anchors, payload) of every entry; the first len(anchors) parts of a key are the anchors' addresses."""
+        return [(k, a, p) for k, (a, p) in self._d.items()]
+
+    def __len__(self):
+        return len(self._d)
+
+
 # "hpf" mode: kernels that produce an f32 activation also write its bf16 twin in the same pass (LayerNorm, BatchNorm +
 # activation, the split GEMM / convolution epilogues -- ops.TWIN); _A() picks the twin up when the tensor is saved for the
-# backward pass, and falls back to a cast launch for tensors nobody twinned.  Entries keep both tensors alive, are popped on
-# use and dropped by new_step().
-_twins = {}
-_twin_stats = {"made": 0, "used": 0}
+# backward pass, and falls back to a cast launch for tensors nobody twinned.  Entries (anchor: the f32 / f16 tensor, payload:
+# its twin) are popped on use and dropped by new_step().
+_twins = _HandOff("twins", 256)
+_twin_stats = {"made": 0, "used": 0, "cast": 0}
 _TWIN_MIN = 1 << 15  # elements: below this a cast launch at save time costs nothing worth a second output stream
 
 
@@ -157,12 +203,21 @@ def _make_twin(y):
         return None
     if y.numel() < _TWIN_MIN or not y.is_contiguous():
         return None
-    if len(_twins) > 256:
-        _twins.clear()
-    t = torch.empty(y.shape, dtype=torch.bfloat16, device=y.device)
-    _twins[y.data_ptr()] = (y, t)
     _twin_stats["made"] += 1
-    return t
+    return _twins.put(torch.empty(y.shape, dtype=torch.bfloat16, device=y.device), y)
+
+
+def _twin_of(t):
+    """The registered bf16 twin of (all of) the contiguous tensor t, or None; it stays registered."""
+    ent = _twins.get(t)
+    return ent[1] if ent is not None and ent[0][0].numel() == t.numel() else None
+
+
+def _cast_twin(t, count=True):
+    """No producer-side twin (tensors below _TWIN_MIN, evaluation-mode producers, pooled outputs): cast one and register it."""
+    if count:
+        _twin_stats["cast"] += 1
+    return _twins.put(ops.scale_dropout(t, torch.bfloat16), t)
 
 
 def _A(t):
@@ -170,11 +225,11 @@ def _A(t):
     backward pass gets a bf16 copy; identity in the other modes."""
     if t is None or not _state["hpf"] or t.dtype not in (torch.float32, torch.float16):
         return t
-    ent = _twins.pop(t.data_ptr(), None) if t.is_contiguous() else None
-    if ent is not None and ent[0].numel() == t.numel():  # (views of the producer's buffer: same bytes, another shape)
+    ent = _twins.pop(t) if t.is_contiguous() else None
+    if ent is not None and ent[0][0].numel() == t.numel():  # (views of the producer's buffer: same bytes, another shape)
         _twin_stats["used"] += 1
         return ent[1].view(t.shape)
-    _twin_stats["cast"] = _twin_stats.get("cast", 0) + 1
+    _twin_stats["cast"] += 1
     return ops.scale_dropout(t.contiguous(), torch.bfloat16)
 
 
@@ -184,54 +239,48 @@ def _A_view(t, base):
     (several views of one base are saved)."""
     if t is None or not _state["hpf"] or t.dtype not in (torch.float32, torch.float16):
         return t
-    ent = _twins.get(base.data_ptr())
     if t.dtype != base.dtype or not base.is_contiguous():
         return _A(t)
-    if ent is None or ent[0].numel() != base.numel():
-        # no producer-side twin (tensors below _TWIN_MIN, evaluation-mode producers): ONE cast of the base, shared by all of its
-        # views -- the backward kernels address their outputs with the strides of these views, so the layout must be kept
-        if len(_twins) > 256:
-            _twins.clear()
-        _twin_stats["cast"] = _twin_stats.get("cast", 0) + 1
-        ent = _twins[base.data_ptr()] = (base, ops.scale_dropout(base, torch.bfloat16))
+    tw = _twin_of(base)
+    if tw is None:
+        # ONE cast of the base, shared by all of its views -- the backward kernels address their outputs with the strides of
+        # these views, so the layout must be kept
+        tw = _cast_twin(base)
     off = (t.data_ptr() - base.data_ptr()) // t.element_size()
     _twin_stats["used"] += 1
-    return ent[1].as_strided(t.shape, t.stride(), ent[1].storage_offset() + off)
+    return tw.as_strided(t.shape, t.stride(), tw.storage_offset() + off)
 
 
 # hpf mode, front-end trunk: consecutive trunk functions hand their activation over as the bf16 TWIN (the autograd-visible
-# tensor) plus, through this registry, the f32 original for the next function's precise forward.  With f32 outputs autograd
+# tensor) plus, through this table, the f32 original for the next function's precise forward.  With f32 outputs autograd
 # itself cast every bf16 data gradient up to the forward dtype and the next function cast it back down -- two passes over the
-# largest activations of the step per trunk function.
-_f32_of = {}
+# largest activations of the step per trunk function.  Entries (anchor: the twin, payload: the original) hold BOTH tensors
+# until new_step(): the twin's address cannot go to another bf16 tensor while its entry answers for it.
+_f32_of = _HandOff("f32_of", 64)
 
 
 def _hand_over(out):
     """f32 output of a trunk function -> its bf16 twin as the tensor autograd sees (hpf mode, twin available); else `out`."""
     if not _state["hpf"] or out.dtype not in (torch.float32, torch.float16):
         return out
-    ent = _twins.get(out.data_ptr())
-    if (ent is None or ent[0].numel() != out.numel()) and out.dtype == torch.float16 and _state.get("tag_ok", False) \
-            and out.is_contiguous():
+    tw = _twin_of(out)
+    if tw is None and out.dtype == torch.float16 and _state.get("tag_ok", False) and out.is_contiguous():
         # an f16 tensor must not be the autograd-visible output: autograd would convert the consumer's bf16 data gradient to f16
-        # (5 exponent bits: gradients below 6e-8 vanish).  No producer-side twin (tensors below _TWIN_MIN): cast one here.
-        _twin_stats["cast"] = _twin_stats.get("cast", 0) + 1
-        ent = _twins[out.data_ptr()] = (out, ops.scale_dropout(out, torch.bfloat16))
-    if ent is None or ent[0].numel() != out.numel():
+        # (5 exponent bits: gradients below 6e-8 vanish)
+        tw = _cast_twin(out)
+    if tw is None:
         return out
-    tw = ent[1].view(out.shape)
-    if len(_f32_of) > 64:
-        _f32_of.clear()
-    _f32_of[tw.data_ptr()] = out
+    tw = tw.view(out.shape)
+    _f32_of.put(out, tw)
     return tw
 
 
 def _f32_in(x):
     """The f32 / f16 original of a handed-over twin (identity for anything else)."""
     if x.dtype == torch.bfloat16 and _state["hpf"]:
-        o = _f32_of.get(x.data_ptr())
-        if o is not None and o.numel() == x.numel():
-            return o.view(x.shape)
+        ent = _f32_of.get(x)
+        if ent is not None and ent[1].numel() == x.numel():
+            return ent[1].view(x.shape)
     return x
 
 
@@ -829,7 +878,8 @@ def _bias3(bq, bk, bv):
     return torch.cat([bq, bk, bv])
 
 
-_pos_proj = {}  # (pos_emb address, linear_pos weight address) -> shared projection of the step (functional_attention.prepare_pos_proj)
+# anchors (pos_emb, linear_pos weight) -> (column block, autograd output, layer slot, holder) of the step's shared projection
+_pos_proj = _HandOff("pos_proj")  # (written and cleared by functional_attention.prepare_pos_proj)
 
 def _fast_ok(a, K, lda):
     return (not _state["precise"]) and a.dtype == torch.bfloat16 and K % 64 == 0 and (lda or K) % 8 == 0
@@ -933,14 +983,10 @@ _arena = _ZeroArena()
 
 def new_step():
     """Call at the start of every training step that may be captured into a hipGraph (bench.py, train_native.py):
-    makes the zero-scratch arena start the step on a chunk whose fill belongs to the capture."""
+    makes the zero-scratch arena start the step on a chunk whose fill belongs to the capture, and drops the hand-off tables."""
     _arena.new_step()
-    _chain_spec.clear()
-    _chain_g.clear()
-    _shared_act.clear()
-    _pos_proj.clear()
-    _twins.clear()
-    _f32_of.clear()
+    for tab in _tables:
+        tab.clear()
 
 
 def _zeros(shape, device):
@@ -962,16 +1008,15 @@ def _fast_mode(t):
 # LayerNorm backward, whose result dx is exactly the output gradient of sub-layer k: the kernel can emit that sub-layer's
 # backward prologue -- g = bf16(alpha_k * dropout_k(dx)) and the bias gradient colsum(g) -- in the same pass
 # (avsr_layernorm_bwd gout / gsum) instead of a separate cast / column-sum launch over dx.  Autograd functions cannot see
-# their neighbours, so the hand-off goes through two small registries keyed by device address:
+# their neighbours, so the hand-off goes through two hand-off tables (_HandOff) keyed by device address:
 #   forward : sub-layer k tags its output with its prologue parameters; sub-layer k+1 (or a bare LayerNorm) picks the tag
 #             up from its input and remembers it for its backward pass;
 #   backward: the LayerNorm backward leaves (g, db) under the address of the dx it returns; sub-layer k's _prologue finds
 #             it under the address of the dy it was handed (autograd passes the tensor through unchanged when the residual
 #             has a single consumer; any copy / accumulation simply misses and the ordinary prologue runs).
-# Entries hold the tensors they describe alive (an address cannot be recycled while its entry exists) and are dropped by
-# new_step(); a stale tag can at worst make a LayerNorm backward emit a prologue nobody uses.
-_chain_spec = {}
-_chain_g = {}
+# Entries are dropped by new_step(); a stale tag can at worst make a LayerNorm backward emit a prologue nobody uses.
+_chain_spec = _HandOff("chain_spec", 512)  # anchor y -> spec
+_chain_g = _HandOff("chain_g", 512)  # anchor dx -> (g, spec)
 _CHAIN = os.environ.get("AVSR_CHAIN_PROLOGUE", "1") != "0"
 
 
@@ -982,16 +1027,14 @@ def _chain_tag(y, rows, n, alpha, drop):
     if not _state.get("tag_ok", True):
         return  # the sub-layer runs under no_grad (evaluation / decoding): no backward pass will ever consume the tag, it
                 # would only keep the activation alive (beam search with the decoder cache piled up hundreds of them)
-    if len(_chain_spec) > 512:
-        _chain_spec.clear()
     p, sd, sdev = drop
-    _chain_spec[y.data_ptr()] = (y, (rows, n, float(alpha), float(p), int(sd), sdev))
+    _chain_spec.put((rows, n, float(alpha), float(p), int(sd), sdev), y)
 
 
 def _chain_take(x):
     """Forward of the consumer of a residual-stream tensor: the producer's tag, if x is one."""
-    ent = _chain_spec.pop(x.data_ptr(), None)
-    if ent is None or ent[0] is not x and ent[0].data_ptr() != x.data_ptr() or tuple(ent[0].shape) != tuple(x.shape):
+    ent = _chain_spec.pop(x)
+    if ent is None or tuple(ent[0][0].shape) != tuple(x.shape):
         return None
     return ent[1]
 
@@ -1005,18 +1048,16 @@ def _ln_bwd(dh, x, ln_w, mean, rstd, dg, dbt, dres, spec):
     # (the bias gradient colsum(g) is taken by the weight-gradient GEMM that contracts g, _wgrad(bias_out=...): column sums
     # out of this kernel cost ~145 k float atomics per launch -- measured +3.5 us on a 9.5 us kernel)
     dx = ops.layernorm_bwd(dh, x, ln_w, mean, rstd, dg, dbt, dres=dres, gout=g, alpha=alpha, drop_p=p, seed=sd, seed_dev=sdev)
-    if len(_chain_g) > 512:
-        _chain_g.clear()
-    _chain_g[dx.data_ptr()] = (dx, g, spec)
+    _chain_g.put((g, spec), dx)
     return dx
 
 
 def _chain_prologue(src, rows, n, alpha, drop):
-    ent = _chain_g.pop(src.data_ptr(), None)
+    ent = _chain_g.pop(src)
     if ent is None:
         return None
     p, sd, sdev = drop
-    dx, g, spec = ent
+    (dx,), (g, spec) = ent
     if spec[:5] != (rows, n, float(alpha), float(p), int(sd)) or spec[5] is not sdev or dx.shape != src.shape:
         return None
     return g.view(rows, n)
@@ -1109,36 +1150,30 @@ def _to_act(x):
     return ops.scale_dropout(x.contiguous(), act_dtype())
 
 
-_shared_act = {}
+_shared_act = _HandOff("shared_act", 8)  # anchor: the source; extra: shape, dtypes / save tag, version -> the copy
 
 
 def _to_act_shared(x):
     """_to_act for a tensor that SEVERAL sub-layers of one step consume unchanged -- the encoder memory (6 decoder layers'
     source attention) and the relative-position table (12 encoder layers): the activation-dtype copy is made once per step
-    and shared.  Entries keep their source alive (its address cannot be recycled meanwhile) and are dropped by new_step();
-    outside a step loop the cache is bounded."""
+    and shared.  Entries are dropped by new_step(); outside a step loop the cache is bounded."""
     if x.dtype == act_dtype() and x.is_contiguous():
         return x
-    key = (x.data_ptr(), tuple(x.shape), x.dtype, act_dtype(), x._version)
-    ent = _shared_act.get(key)
-    if ent is None:
-        if len(_shared_act) > (8 if x.requires_grad else 2):  # decoding never calls new_step(): keep the cache tiny there
-            _shared_act.clear()
-        ent = _shared_act[key] = (x, ops.scale_dropout(x.contiguous(), act_dtype()))
-    return ent[1]
+    extra = (tuple(x.shape), x.dtype, act_dtype(), x._version)
+    ent = _shared_act.get(x, extra=extra)
+    if ent is not None:
+        return ent[1]
+    # (decoding never calls new_step(): keep the cache tiny there)
+    return _shared_act.put(ops.scale_dropout(x.contiguous(), act_dtype()), x, extra=extra, cap=None if x.requires_grad else 2)
 
 
 def _A_shared(t):
     """_A for a tensor that several sub-layers of one step save unchanged (encoder memory, position table)."""
     if t is None or not _state["hpf"] or t.dtype not in (torch.float32, torch.float16):
         return t
-    key = (t.data_ptr(), tuple(t.shape), "hpf-save", t._version)
-    ent = _shared_act.get(key)
-    if ent is None:
-        if len(_shared_act) > 8:
-            _shared_act.clear()
-        ent = _shared_act[key] = (t, ops.scale_dropout(t.contiguous(), torch.bfloat16))
-    return ent[1]
+    extra = (tuple(t.shape), "hpf-save", t._version)
+    ent = _shared_act.get(t, extra=extra)
+    return ent[1] if ent is not None else _shared_act.put(ops.scale_dropout(t.contiguous(), torch.bfloat16), t, extra=extra)
 
 
 def _to_f32(x):

@@ -34,7 +34,7 @@ def prepare_pos_proj(pos_emb, weights):
         holder = {}
         out = PosProjFn.apply(pos_emb, holder, *weights)
         for i, w in enumerate(weights):
-            _pos_proj[(pos_emb.data_ptr(), w.data_ptr())] = (pos_emb, None, out, i, holder)
+            _pos_proj.put((None, out, i, holder), pos_emb, w)
         return
     out = torch.empty(P, n * D, dtype=pe.dtype, device=pe.device)
     if pe.dtype == torch.float16:
@@ -42,7 +42,13 @@ def prepare_pos_proj(pos_emb, weights):
     else:
         ops.gemm_bf16_nt(pe, D, _w_bf16_cat(tuple(weights), False), D, P, n * D, D, out, n * D)
     for i, w in enumerate(weights):
-        _pos_proj[(pos_emb.data_ptr(), w.data_ptr())] = (pos_emb, out[:, i * D:(i + 1) * D], None, i, None)
+        _pos_proj.put((out[:, i * D:(i + 1) * D], None, i, None), pos_emb, w)
+
+
+def _shared_pos_proj(pos_emb, wpos):
+    """What prepare_pos_proj left for this layer: (column block without autograd, autograd output, slot, holder), else Nones."""
+    ent = _pos_proj.get(pos_emb, wpos)
+    return ent[1] if ent is not None else (None,) * 4
 
 
 _placeholders = {}
@@ -267,11 +273,11 @@ class MhaSublayerFn(torch.autograd.Function):
         pe = pproj = qv = None
         if relpos:
             pe = _to_act_shared(pos_emb).reshape(-1, D)
-            pre = _pos_proj.get((pos_emb.data_ptr(), wpos.data_ptr())) if pp_all is None else None
+            pre = _shared_pos_proj(pos_emb, wpos)[0] if pp_all is None else None
             if pp_all is not None:
                 pproj = pp_all[:, pp_slot * D:(pp_slot + 1) * D]  # column block of the all-layer projection (PosProjFn)
-            elif pre is not None and pre[1] is not None and pre[1].dtype == T:
-                pproj = pre[1]  # the same, without autograd (prepare_pos_proj under no_grad), row pitch n_layers * D
+            elif pre is not None and pre.dtype == T:
+                pproj = pre  # the same, without autograd (prepare_pos_proj under no_grad), row pitch n_layers * D
             else:
                 pproj = torch.empty(pe.shape[0], D, dtype=T, device=x.device)
                 _gemm_nt(pe, wpos, pe.shape[0], D, D, pproj)
@@ -436,11 +442,11 @@ def mha_sublayer(x, memory, pos_emb, mask, ln_w, ln_b, wq, bq, wk, bk, wv, bv, w
         return MhaSublayerFn.apply(_to_f32(x), None, pos_emb, mask, ln_w, ln_b, wq, bq, wk, bk, wv, bv, wo, bo, wpos,
                                    bias_u, bias_v, H, float(p_attn), float(p_out), eps, kv[0], kv[1], kv[2])
     if pos_emb is not None and wpos is not None:
-        pre = _pos_proj.get((pos_emb.data_ptr(), wpos.data_ptr()))
-        if pre is not None and pre[2] is not None and torch.is_grad_enabled():
+        _, pp_all, pp_slot, pp_holder = _shared_pos_proj(pos_emb, wpos)
+        if pp_all is not None and torch.is_grad_enabled():
             return MhaSublayerFn.apply(_to_f32(x), memory, pos_emb, mask, ln_w, ln_b, wq, bq, wk, bk, wv, bv, wo, bo, wpos,
-                                       bias_u, bias_v, H, float(p_attn), float(p_out), eps, None, 0, None, pre[2], pre[3],
-                                       pre[4])
+                                       bias_u, bias_v, H, float(p_attn), float(p_out), eps, None, 0, None, pp_all, pp_slot,
+                                       pp_holder)
     return MhaSublayerFn.apply(_to_f32(x), memory, pos_emb, mask, ln_w, ln_b, wq, bq, wk, bk, wv, bv, wo, bo, wpos,
                                bias_u, bias_v, H, float(p_attn), float(p_out), eps)
 

@@ -8,7 +8,7 @@ import torch
 from . import functional as AF
 from . import ops
 from .functional import (  # noqa: F401
-    _A, _act_in, _bwd_mode, _bwd_precise, _f32_in, _hand_over, _state, _to_act, _to_f32, _twins, _w_conv,
+    _A, _act_in, _bwd_mode, _bwd_precise, _cast_twin, _f32_in, _hand_over, _state, _to_act, _to_f32, _twin_of, _w_conv,
     _w_conv_fwd, act_dtype, padded_cols)
 from .functional_convmod import _bn_train_stats_pair  # noqa: F401
 from .functional_convmod import (  # noqa: F401
@@ -231,9 +231,9 @@ class StemFn(torch.autograd.Function):
             out = ops.bn_act_fwd(c0, None, m0, i0, g, b, rows, Cout, 1)
         ctx.save_for_backward(x, _A(c0), idx, g, b, m0, i0, n0, _A(xsel))
         ctx.meta = (geom, pool, training, bn_rest, (OH, OW), w.shape, geom_ok and not _bwd_precise())
-        if _state["hpf"] and out.dtype == torch.float32 and out.data_ptr() not in _twins and _state.get("tag_ok", True):
+        if _state["hpf"] and out.dtype == torch.float32 and _twin_of(out) is None and _state.get("tag_ok", True):
             # (the pooled output has no producer-side twin: make it here -- the first residual block would cast it anyway)
-            _twins[out.data_ptr()] = (out, ops.scale_dropout(out, torch.bfloat16))
+            _cast_twin(out, count=False)
         return _hand_over(out)
 
     @staticmethod

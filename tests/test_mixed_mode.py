@@ -395,7 +395,7 @@ def test_e2e_small_mixed_mode(dev, modality, policy, monkeypatch):
     -- policy {} -- bit-identical to the hpf mode (everything on split planes)."""
     from oracle import avsr_oracle as O
     from synth import synth_state_dict
-    from test_modules import no_dropout, synth_batch
+    from test_modules import no_dropout, synth_batch, watch_handoff_tables
 
     from auto_avsr_amd.e2e import E2E
 
@@ -421,10 +421,19 @@ def test_e2e_small_mixed_mode(dev, modality, policy, monkeypatch):
     AF.invalidate_weight_cache()
     monkeypatch.setattr(AF, "_TWIN_MIN", (1 << 60) if policy == "default-casts" else 0)
     AF._twin_stats.update(made=0, used=0, cast=0)
+    walk, puts = watch_handoff_tables(monkeypatch)
+    AF.new_step()
     with AF.numerics("mixed"):
         assert AF.mode() == "mixed"
         loss, loss_ctc, loss_att, acc = m(x.to(dev), lengths.to(dev), y.to(dev))
+        held = walk()  # between the passes
         loss.backward()
+    walk()
+    assert held["twins"] > 0 and held["f32_of"] > 0 and held["shared_act"] > 0, held
+    if policy != "all-split":  # (split planes everywhere: no shared position projection and, as in the hpf mode, no chaining)
+        # the chain tags are all taken by their consumers within the forward pass, the chained gradients within the backward
+        # pass: their entries were checked as they were made
+        assert held["pos_proj"] > 0 and puts["chain_spec"] > 0 and puts["chain_g"] > 0, (held, puts)
     assert AF.mode() == "bf16" and ops.TWIN is None and not AF._state["f16"]
     assert abs(float(loss_ctc) - float(ctc_r)) < 1e-3 * abs(float(ctc_r))
     assert abs(float(loss_att) - float(att_r)) < 1e-3 * abs(float(att_r))

@@ -1,6 +1,8 @@
 """Module-level parity of the HIP-backed nn.Module tree against (a) the reference-generated golden vectors and
 (b) the oracle, in precise mode (split-bf16 contractions) with dropout off.  Runs on the emulator build in the
 CPU suite and on the gfx950 build under -m gpu."""
+import collections
+import gc
 import os
 import sys
 
@@ -42,6 +44,61 @@ def check_grad_norms(model, ref_norms, rtol):
         if abs(got - ref_norms[k]) > rtol * ref_norms[k] + atol:
             bad.append((k, got, ref_norms[k]))
     assert not bad, bad[:6]
+
+
+def watch_handoff_tables(monkeypatch):
+    """functional.py's address-keyed hand-off tables while a step runs.  The invariant -- every address in an entry's key is the
+    data_ptr() of a tensor that entry holds, so the address cannot have gone to another tensor -- is checked on a table after each
+    put() and on all registered tables by the returned walk(), which gives {table name: entries}.  Also returned: the number of
+    entries each table received (the chain tables fill and drain inside one pass: a walk between the passes finds them empty)."""
+    puts = collections.Counter()
+
+    def check(tab):
+        for key, anchors, _ in tab.items():
+            assert anchors and all(isinstance(a, torch.Tensor) for a in anchors), tab.name
+            assert key[:len(anchors)] == tuple(a.data_ptr() for a in anchors), (tab.name, key)
+        return len(tab)
+
+    real = AF._HandOff.put
+
+    def put(self, *args, **kw):
+        out = real(self, *args, **kw)
+        puts[self.name] += 1
+        check(self)
+        return out
+
+    monkeypatch.setattr(AF._HandOff, "put", put)
+    return (lambda: {tab.name: check(tab) for tab in AF._tables}), puts
+
+
+def test_hand_over_entry_holds_its_twin():
+    """A handed-over twin that its consumer has saved and autograd has released: while the hand-over entry exists it holds the twin,
+    so no later bf16 tensor of the same size gets the twin's address and is answered with an unrelated f32 original.  (With entries
+    that held the original only, 15 to 18 of these 20 trials returned a stale tensor.)"""
+    state, stats = dict(AF._state), dict(AF._twin_stats)
+    AF.new_step()
+    try:
+        AF._state.update(hpf=True, precise=True, tag_ok=True)
+        addrs, reused, stale = set(), 0, 0
+        for _ in range(20):
+            out = torch.randn(4, 1 << 14)
+            tw = AF._make_twin(out)  # (what a producing kernel's wrapper does)
+            h = AF._hand_over(out)
+            assert h.dtype == torch.bfloat16 and h.data_ptr() == tw.data_ptr() and AF._f32_in(h).data_ptr() == out.data_ptr()
+            AF._A(out)  # the consumer saves the twin: popped from the twin table
+            addrs.add(tw.data_ptr())
+            del tw, h
+            gc.collect()
+            z = torch.zeros(4, 1 << 14, dtype=torch.bfloat16)
+            reused += z.data_ptr() in addrs
+            stale += AF._f32_in(z) is not z
+        assert len(AF._f32_of) == 20
+        assert (reused, stale) == (0, 0), f"{reused} fresh tensors at a registered twin's address, {stale} stale originals returned"
+    finally:
+        AF._state.clear()
+        AF._state.update(state)
+        AF._twin_stats.update(stats)
+        AF.new_step()
 
 
 def test_encoder_small_vs_reference_golden(dev, golden):
@@ -163,10 +220,16 @@ def test_e2e_small_hpf_mode(dev, modality, twins, monkeypatch):
     # cast: every saved activation is cast at save time -- the two must agree bit for bit
     monkeypatch.setattr(AF, "_TWIN_MIN", 0 if twins else 1 << 60)
     AF._twin_stats.update(made=0, used=0)
+    walk, puts = watch_handoff_tables(monkeypatch)
+    AF.new_step()
     with AF.numerics("hpf"):
         assert AF.mode() == "hpf"
         loss, loss_ctc, loss_att, acc = m(x.to(dev), lengths.to(dev), y.to(dev))
+        held = walk()  # between the passes
         loss.backward()
+    walk()
+    # (no chain tags here: the hpf forward is the precise one, which does not chain -- test_mixed_mode.py walks those)
+    assert held["twins"] > 0 and held["f32_of"] > 0 and held["shared_act"] > 0, held
     if twins:
         assert AF._twin_stats["used"] > 20 and AF._twin_stats["used"] >= 0.9 * AF._twin_stats["made"] - 2, AF._twin_stats
     else:
