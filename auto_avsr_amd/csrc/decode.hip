@@ -772,8 +772,60 @@ __global__ __launch_bounds__(SEL_NT) void logsoftmax_prebeam_kernel(const float*
 // or not the pre-beam kept it; every other token outside the candidates carries the CTC scorer's LOGZERO and cannot
 // reach a beam of K <= n * (S - 1) -- the host refuses configurations where it could).  Arithmetic order as the python
 // form: ((w_dec * logp [+ w_lm * lm_logp] + w_len) + w_ctc * (log_psi - s_prev)) + score, f32; the language model's term
-// (shallow fusion, scorers["lm"]) only with a session that carries one.  ONE block: radix select of the
+// (shallow fusion, scorers["lm"]) only with a session that carries one, then, with a bias list, + w_bias * gain (the order of the
+// python step over the full scorers: decoder, lm, bias, length_bonus).  ONE block: radix select of the
 // K best values, then a rank sort of those K (value descending, entry ascending).
+// ---------------------------------------------------------------------------------------------------------------------
+// Contextual biasing (auto_avsr_amd/bias.py: ContextBiasScorer): a trie of phrases in CSR form -- node s owns the edges
+// [first[s], first[s + 1]) with tokens tok[] ascending and targets child[] (an end node without children already replaced by the
+// root 0), unc[s] = edges from s up to its nearest end ancestor-or-self (or the root).  A hypothesis carries one node.
+struct BiasTab {
+    const int *first, *tok, *child, *unc;
+    int n_nodes;  // 0: no list
+};
+
+// edge of node s on token v, -1 if there is none: binary search among the node's children
+AVSR_DEV int bias_edge(const BiasTab& t, int s, int v) {
+    int lo = t.first[s], hi = t.first[s + 1];
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int x = t.tok[mid];
+        if (x == v) return mid;
+        if (x < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return -1;
+}
+
+// gain of extending a hypothesis at node s by token v and the node it reaches: +1 along an edge; otherwise the uncommitted reward of
+// s is taken back and v alone is retried from the root (no failure links)
+AVSR_DEV int bias_gain(const BiasTab& t, int s, int v, int& next) {
+    int e = bias_edge(t, s, v);
+    if (e >= 0) {
+        next = t.child[e];
+        return 1;
+    }
+    int g = -t.unc[s];
+    next = 0;
+    if (s != 0 && (e = bias_edge(t, 0, v)) >= 0) {
+        next = t.child[e];
+        g += 1;
+    }
+    return g;
+}
+
+// the lookup on its own (avsr_bias_score): entry (row, c) of gain / next [n][S + 1], column S = <eos>
+__global__ __launch_bounds__(256) void bias_score_kernel(BiasTab t, const int* __restrict__ node, const int64_t* __restrict__ cand, int n, int S,
+                                                         int eos, float* __restrict__ gain, int* __restrict__ next) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)n * (S + 1)) return;
+    const int row = (int)(i / (S + 1)), c = (int)(i - (long)row * (S + 1));
+    int g = 0, nx = 0;
+    if (t.n_nodes > 0) g = bias_gain(t, node[row], c < S ? (int)cand[(size_t)row * S + c] : eos, nx);
+    gain[i] = (float)g;
+    next[i] = nx;
+}
+
 struct SelectArgs {
     const float* logp;  // [n][ld] decoder log-probabilities
     long ld;
@@ -784,8 +836,12 @@ struct SelectArgs {
     float w_dec, w_ctc, w_len;
     const float* lm_logp;  // [n][ld] language-model log-probabilities, NULL: no language model
     float w_lm;
-    int* sel;     // [K][4]: prev, tok, candidate column (-1: <eos> outside the candidates), spare
+    int* sel;     // [K][4]: prev, tok, candidate column (-1: <eos> outside the candidates), trie node reached (0 without a bias list)
     float* selv;  // [K][4]: total, decoder term logp, ctc term (log_psi - s_prev), ctc log_psi
+    BiasTab bias;      // contextual biasing: the trie, n_nodes == 0 without a list
+    const int* node;   // [n] trie node of every hypothesis
+    float w_bias;
+    float* selg;       // [K] gain of the selected extensions
 };
 
 // row0: the packed row of the utterance's hypothesis 0 (what `prev` counts from; 0 for a search of one utterance)
@@ -826,6 +882,10 @@ AVSR_DEV void beam_select_block(char* smem, RadixScratch& sc, const SelectArgs& 
         if (decode(e, b, c, tok, dec, ctc_rel, log_psi)) {
             float w = a.w_dec * dec;
             if (a.lm_logp) w = w + a.w_lm * a.lm_logp[(size_t)b * a.ld + tok];
+            if (a.bias.n_nodes) {
+                int nx;
+                w = w + a.w_bias * (float)bias_gain(a.bias, a.node[b], tok, nx);
+            }
             if (a.has_len) w = w + a.w_len;
             w = w + a.w_ctc * ctc_rel;
             v = w + a.score[b];
@@ -855,7 +915,9 @@ AVSR_DEV void beam_select_block(char* smem, RadixScratch& sc, const SelectArgs& 
         a.sel[4 * rank + 0] = row0 + b;
         a.sel[4 * rank + 1] = tok;
         a.sel[4 * rank + 2] = c;
-        a.sel[4 * rank + 3] = 0;
+        int nx = 0;
+        if (a.bias.n_nodes) a.selg[rank] = (float)bias_gain(a.bias, a.node[b], tok, nx);
+        a.sel[4 * rank + 3] = nx;
         a.selv[4 * rank + 0] = v;
         a.selv[4 * rank + 1] = dec;
         a.selv[4 * rank + 2] = ctc_rel;
@@ -886,6 +948,10 @@ __global__ __launch_bounds__(SEL_NT) void beam_select_group_kernel(SelectArgs a,
     a.n = d.n;
     a.sel += 4 * d.noff;
     a.selv += 4 * d.noff;
+    if (a.bias.n_nodes) {
+        a.node += d.off;
+        a.selg += d.noff;
+    }
     beam_select_block(smem, sc, a, d.off);
 }
 
@@ -897,6 +963,8 @@ struct BeamBuf {
     int64_t* last;  // [beam] last token
     float* sc;      // [6][beam]: total, decoder sum, ctc sum, length sum, ctc log prefix probability s, language-model sum
     float* r;       // [T][2][n] (pitch = current n)
+    int* node;      // [beam] trie node of the bias list, NULL without one
+    float* bias;    // [beam] running sum of the bias gains, NULL without a list
 };
 
 // new hypothesis k = hypothesis prev[k] extended by tok[k]  (batch_beam_search.py:131-176 merge + select states)
@@ -904,7 +972,8 @@ struct BeamBuf {
 // state is r_new [T][2][n_src][S] -> dst_r [T][2][K]
 AVSR_DEV void beam_update_row(const BeamBuf& src, const BeamBuf& dst, int ldy, int beam, int L, int n_src, int K, int T, int S, int k, int kl,
                               int row0, const int* __restrict__ sel, const float* __restrict__ selv, const float* __restrict__ r_new,
-                              float* __restrict__ dst_r, const float* __restrict__ lm_logp, long ld_lm, float* __restrict__ host_row) {
+                              float* __restrict__ dst_r, const float* __restrict__ lm_logp, long ld_lm, const float* __restrict__ selg,
+                              float* __restrict__ host_row) {
     const int tid = threadIdx.x;
     const int prev = sel[4 * k], tok = sel[4 * k + 1], pl = prev - row0;
     int pos = sel[4 * k + 2];
@@ -934,7 +1003,12 @@ AVSR_DEV void beam_update_row(const BeamBuf& src, const BeamBuf& dst, int ldy, i
         h[4] = s_ctc;
         h[5] = s_len;
         h[6] = s_lm;
-        h[7] = 0.f;
+        float s_bias = 0.f;
+        if (dst.node) {  // the node the select kernel found for (prev, tok) and the running sum of gains
+            dst.node[k] = sel[4 * k + 3];
+            dst.bias[k] = s_bias = src.bias[prev] + selg[k];
+        }
+        h[7] = s_bias;
     }
     // CTC forward variables of (prev, candidate column pos): r_new [T][2][n_src][S] -> dst.r [T][2][K]
     for (int i = tid; i < 2 * T; i += 256) dst_r[(size_t)i * K + kl] = r_new[((size_t)i * n_src + pl) * S + pos];
@@ -943,8 +1017,8 @@ AVSR_DEV void beam_update_row(const BeamBuf& src, const BeamBuf& dst, int ldy, i
 __global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf dst, int ldy, int beam, int L, int n_src, int K, int T, int S,
                                                           const int* __restrict__ sel, const float* __restrict__ selv,
                                                           const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
-                                                          float* __restrict__ host_row) {
-    beam_update_row(src, dst, ldy, beam, L, n_src, K, T, S, blockIdx.x, blockIdx.x, 0, sel, selv, r_new, dst.r, lm_logp, ld_lm, host_row);
+                                                          const float* __restrict__ selg, float* __restrict__ host_row) {
+    beam_update_row(src, dst, ldy, beam, L, n_src, K, T, S, blockIdx.x, blockIdx.x, 0, sel, selv, r_new, dst.r, lm_logp, ld_lm, selg, host_row);
 }
 
 // the utterance that owns row k of the beam being written
@@ -959,11 +1033,11 @@ AVSR_DEV int utt_of_new_row(const Group& g, int k) {
 __global__ __launch_bounds__(256) void beam_update_group_kernel(BeamBuf src, BeamBuf dst, Group grp, int ldy, int pitch, int beam, int L, int S,
                                                                 const int* __restrict__ sel, const float* __restrict__ selv,
                                                                 const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
-                                                                float* __restrict__ host_row) {
+                                                                const float* __restrict__ selg, float* __restrict__ host_row) {
     const int k = blockIdx.x;
     const Utt d = grp.u[utt_of_new_row(grp, k)];
     beam_update_row(src, dst, ldy, pitch, L, d.n, d.nn, d.T, S, k, k - d.noff, d.off, sel, selv, r_new + (size_t)2 * d.f0 * beam * S,
-                    dst.r + (size_t)2 * d.f0 * beam, lm_logp, ld_lm, host_row);
+                    dst.r + (size_t)2 * d.f0 * beam, lm_logp, ld_lm, selg, host_row);
 }
 
 // hypotheses keep.idx[0 .. keep.n) survive (ended ones are taken off the beam, batch_beam_search.py:178-206)
@@ -975,6 +1049,10 @@ __global__ __launch_bounds__(256) void beam_keep_kernel(BeamBuf src, BeamBuf dst
     }
     if (tid < 6) dst.sc[tid * beam + k] = src.sc[tid * beam + from];
     if (tid == 6) dst.last[k] = src.last[from];
+    if (tid == 7 && src.node) {
+        dst.node[k] = src.node[from];
+        dst.bias[k] = src.bias[from];
+    }
     for (int i = tid; i < 2 * T; i += 256) dst.r[(size_t)i * keep.n + k] = src.r[(size_t)i * n_src + from];
 }
 
@@ -988,6 +1066,10 @@ __global__ __launch_bounds__(256) void beam_keep_group_kernel(BeamBuf src, BeamB
     }
     if (tid < 6) dst.sc[tid * pitch + k] = src.sc[tid * pitch + from];
     if (tid == 6) dst.last[k] = src.last[from];
+    if (tid == 7 && src.node) {
+        dst.node[k] = src.node[from];
+        dst.bias[k] = src.bias[from];
+    }
     const float* sr = src.r + (size_t)2 * d.f0 * beam;
     float* dr = dst.r + (size_t)2 * d.f0 * beam;
     const int kl = k - d.noff, fl = from - d.off;
@@ -1000,6 +1082,10 @@ __global__ void beam_init_kernel(BeamBuf st, int beam, int T, int sos, const flo
         st.yseq[0] = sos;
         st.last[0] = sos;
         for (int i = 0; i < 6; i++) st.sc[i * beam] = 0.f;
+        if (st.node) {  // the root of the bias trie
+            st.node[0] = 0;
+            st.bias[0] = 0.f;
+        }
     }
     if (tid < 2 * T) st.r[tid] = r_init[tid];
 }
@@ -1012,6 +1098,10 @@ __global__ void beam_init_group_kernel(BeamBuf st, Group grp, PtrList r_init, in
         st.yseq[(size_t)d.off * ldy] = sos;
         st.last[d.off] = sos;
         for (int i = 0; i < 6; i++) st.sc[i * pitch + d.off] = 0.f;
+        if (st.node) {
+            st.node[d.off] = 0;
+            st.bias[d.off] = 0.f;
+        }
     }
     if (tid < 2 * d.T) st.r[(size_t)2 * d.f0 * beam + tid] = r_init.p[u][tid];
 }
@@ -1038,8 +1128,16 @@ struct Lm {
           *logp = nullptr;
 };
 
+// The bias list a session may carry (avsr_beam_set_bias): device tables owned by the caller.
+struct Bias {
+    BiasTab tab{nullptr, nullptr, nullptr, nullptr, 0};
+    float w = 0.f;
+};
+
 struct Session {
     Lm lm;
+    Bias bias, bias_next;  // the list of the running utterance / group; the list the next avsr_beam_begin* takes over
+    float* selg = nullptr;
     int D, H, FF, V, nl, beam, S, sos, eos, blank, has_len;
     float w_dec, w_ctc, w_len, emb_scale, eps;
     const float *embed, *pe;
@@ -1140,6 +1238,13 @@ void carve(Session& s, Carver& c, size_t rows, size_t T, int Lmax) {
     s.sel = c.take<int>(4 * beam);
     s.selv = c.take<float>(4 * beam);
     s.host_dev = c.take<float>(8 * beam);
+    // a bias list (the one the utterance being begun takes over): per-row node and running sum, gains of the selected entries;
+    // nothing is carved without one, so such a session's workspace is what it was
+    for (int i = 0; i < 2; i++) {
+        s.st[i].node = s.bias_next.tab.n_nodes ? c.take<int>(beam) : nullptr;
+        s.st[i].bias = s.bias_next.tab.n_nodes ? c.take<float>(beam) : nullptr;
+    }
+    s.selg = s.bias_next.tab.n_nodes ? c.take<float>(beam) : nullptr;
     if (s.lm.on) {
         Lm& m = s.lm;
         const size_t Dl = m.D;
@@ -1357,6 +1462,43 @@ extern "C" int avsr_beam_attach_lm(int64_t h, const int32_t* cfg, const float* f
     return 0;
 }
 
+// The trie lookup of contextual biasing on its own (tests, the python-issued step's cross-check): row r stands at node[r]; entry
+// (r, c) of gain / next [n][S + 1] is the gain of extending it by cand[r][c] (c < S) or by <eos> (c = S) and the node reached.
+// n_nodes == 0 (no list): zeros.  The tables are device memory in the layout of `struct BiasTab`; they are not validated.
+extern "C" int avsr_bias_score(const int32_t* first, const int32_t* tok, const int32_t* child, const int32_t* unc, int n_nodes, int n_edges,
+                               const int32_t* node, const int64_t* cand, int n, int S, int eos, float* gain, int32_t* next, hipStream_t stream) {
+    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_BIAS_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_BIAS_MAX_EDGES,
+                 "bias_score: too many nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
+    AVSR_REQUIRE(n >= 1 && S >= 0 && (int64_t)n * (S + 1) <= ((int64_t)1 << 30), "bias_score: bad sizes");
+    const BiasTab t{first, tok, child, unc, n_edges > 0 ? n_nodes : 0};
+    const long total = (long)n * (S + 1);
+    AVSR_LAUNCH(bias_score_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, t, node, cand, n, S, eos, gain, next);
+    AVSR_CHECK_LAUNCH("bias_score");
+    return 0;
+}
+
+// Bind a bias list to a session (contextual biasing, scorers["bias"] / weights["bias"]), or replace / remove the one it has:
+// cfg: n_nodes, n_edges (either 0: no list); fcfg: weight.  May be called at any time after avsr_beam_create, as often as wanted; the
+// list takes effect at the next avsr_beam_begin / avsr_beam_begin_batch (a running utterance keeps the list it began with, whose
+// tables must stay alive until then), and the workspace sizes reported from now on are those of a session with the new list.
+extern "C" int avsr_beam_set_bias(int64_t h, const int32_t* cfg, const float* fcfg, const int32_t* first, const int32_t* tok,
+                                  const int32_t* child, const int32_t* unc) {
+    Session* sp = reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(sp != nullptr, "beam_set_bias: no session");
+    const int n_nodes = cfg[0], n_edges = cfg[1];
+    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_BIAS_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_BIAS_MAX_EDGES,
+                 "beam_set_bias: too many nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
+    Bias b;
+    if (n_nodes > 0 && n_edges > 0) {
+        AVSR_REQUIRE(first && tok && child && unc, "beam_set_bias: missing table");
+        AVSR_REQUIRE(fcfg[0] == fcfg[0], "beam_set_bias: the weight is not a number");
+        b.tab = BiasTab{first, tok, child, unc, n_nodes};
+        b.w = fcfg[0];
+    }
+    sp->bias_next = b;
+    return 0;
+}
+
 extern "C" int64_t avsr_beam_workspace_bytes(int64_t h, int T, int Lmax) {
     Session tmp = *reinterpret_cast<Session*>((intptr_t)h);
     Carver c{nullptr};
@@ -1374,6 +1516,7 @@ extern "C" int avsr_beam_begin(int64_t h, const float* memory, int T, const floa
     Carver c{reinterpret_cast<char*>(ws)};
     carve(s, c, s.beam, T, Lmax);
     AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin: workspace too small");
+    s.bias = s.bias_next;
     s.U = 0;
     s.T = T;
     s.Lmax = Lmax;
@@ -1428,8 +1571,9 @@ static int dec_pass(Session& s, BeamBuf& st, int n, int L, int pitch, const Grou
 
 // One decoding step for the n running hypotheses (all of length L): decoder pass over the new position, pre-beam, CTC
 // prefix scores, top-K, new beam state.  host_out [K][8] f32: token, parent, total score, decoder / ctc / length-bonus
-// sums, language-model sum (0 without one), 0 -- valid on return (the call synchronises the stream).  Returns K through n_out.
-// With a language model attached its pass is issued first, in line on the same stream.
+// sums, language-model sum (0 without one), bias sum (0 without a list) -- valid on return (the call synchronises the stream).  Returns K through n_out.
+// With a language model attached its pass is issued first, in line on the same stream.  A bias list adds no
+// launch: the selection looks the gains up where it forms the scores, the update stores the node reached.
 extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
     AVSR_REQUIRE(s.U == 0, "beam_step: the session runs a group of utterances (avsr_beam_step_batch)");
@@ -1443,10 +1587,10 @@ extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_
     const int NE = n * (s.S + 1);
     const int K = beam;  // n * V >= beam always; the viable entries n * (S - 1) >= beam by the create-time check
     SelectArgs a{s.logp, (long)s.ldv, s.cand, s.psi, s.psi_eos, st.sc + 4 * beam, st.sc, n, s.S, K, s.eos, s.blank, s.has_len,
-                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv};
+                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv, s.bias.tab, st.node, s.bias.w, s.selg};
     AVSR_LAUNCH(beam_select_kernel, dim3(1), dim3(SEL_NT), (size_t)(2 * NE + K + n * s.S + n) * 4, stream, a);
     AVSR_LAUNCH(beam_update_kernel, dim3(K), dim3(256), 0, stream, st, nx, s.ldy, beam, L, n, K, s.T, s.S, (const int*)s.sel,
-                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, s.host_dev);
+                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, (const float*)s.selg, s.host_dev);
     AVSR_CHECK_LAUNCH("beam_step");
     const int e = avsr_copy_to_host_sync(host_out, s.host_dev, (size_t)K * 8 * sizeof(float), stream);
     if (e != 0) {
@@ -1541,6 +1685,7 @@ extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memor
     Carver c{reinterpret_cast<char*>(ws)};
     carve(s, c, (size_t)U * s.beam, frames, Lmax);
     AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin_batch: workspace too small");
+    s.bias = s.bias_next;
     s.U = U;
     s.T = s.Tmax = Tmax;
     s.Lmax = Lmax;
@@ -1596,10 +1741,10 @@ extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipS
     DEC_TRY(avsr_ctc_prefix_score_batch(U, s.u_logp, Ts, s.u_ld, s.V, st.r, st.last, s.cand, off, cnt, f0, beam, s.S, L - 1, s.blank, s.r_new,
                                         s.psi, s.psi_eos, stream));
     SelectArgs a{s.logp, (long)s.ldv, s.cand, s.psi, s.psi_eos, st.sc + 4 * pitch, st.sc, 0, s.S, beam, s.eos, s.blank, s.has_len,
-                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv};
+                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv, s.bias.tab, st.node, s.bias.w, s.selg};
     AVSR_LAUNCH(beam_select_group_kernel, dim3(U), dim3(SEL_NT), (size_t)(2 * n_max * (s.S + 1) + beam + n_max * s.S + n_max) * 4, stream, a, g);
     AVSR_LAUNCH(beam_update_group_kernel, dim3(K), dim3(256), 0, stream, st, nx, g, s.ldy, pitch, beam, L, s.S, (const int*)s.sel,
-                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, s.host_dev);
+                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, (const float*)s.selg, s.host_dev);
     AVSR_CHECK_LAUNCH("beam_step_batch");
     const int e = avsr_copy_to_host_sync(host_out, s.host_dev, (size_t)K * 8 * sizeof(float), stream);
     if (e != 0) {

@@ -72,8 +72,16 @@ class NativeBeam:
             return False
         if "decoder" not in full or not isinstance(full["decoder"], TransformerDecoder):
             return False
-        if set(full) - {"decoder", "length_bonus", "lm"}:
+        if set(full) - {"decoder", "length_bonus", "lm", "bias"}:
             return False
+        if "bias" in full:  # contextual biasing: this build's trie scorer, nothing else in that slot
+            from .bias import ContextBiasScorer
+
+            if not isinstance(full["bias"], ContextBiasScorer) or full["bias"].n_vocab != bs.n_vocab:
+                return False
+            # as with a language model: the step's pre-beam ranks the decoder's log-probabilities alone
+            if bs.pre_beam_score_key != "decoder":
+                return False
         if "lm" in full:  # shallow fusion: this build's TransformerLM in a geometry the session takes, nothing else
             from .lm import TransformerLM
 
@@ -117,6 +125,7 @@ class NativeBeam:
         if lm is not None:
             key += (lm_pe.data_ptr(), lm_pe.shape[0], float(bs.weights["lm"]))
         if key == self.key:
+            self._bind_bias(dev)
             return
         L = _lib.lib()
         if self.handle:
@@ -176,6 +185,29 @@ class NativeBeam:
         self.host = torch.empty(MAX_BEAM * 8, dtype=torch.float32, pin_memory=pin)
         self.host_np = self.host.numpy().reshape(MAX_BEAM, 8)
         self.yseq_host = None
+        self.bias_key = None
+        self._bind_bias(dev)
+
+    def _bind_bias(self, dev):
+        """The bias list of scorers["bias"] (avsr_beam_set_bias): re-sent when the list's version or its weight changed, or the
+        session is new -- never a reason to rebuild the session.  Takes effect at the next avsr_beam_begin / _begin_batch."""
+        sc = self.bs.full_scorers.get("bias")
+        if sc is None:
+            if getattr(self, "bias_key", None) is not None:  # the scorer left the search after a list was bound: detach it
+                cfg, fcfg = (ctypes.c_int32 * 2)(0, 0), (ctypes.c_float * 1)(0.0)
+                self.lib.call("avsr_beam_set_bias", self.handle, ctypes.cast(cfg, ctypes.c_void_p), ctypes.cast(fcfg, ctypes.c_void_p),
+                              None, None, None, None)
+                self.bias_key, self.bias_keep = None, None
+            return
+        key = (id(sc), sc.version, float(self.bs.weights["bias"]), str(dev))
+        if key == self.bias_key:
+            return
+        tabs = sc.device_tables(dev)
+        cfg = (ctypes.c_int32 * 2)(sc.n_nodes if sc.n_edges else 0, sc.n_edges)
+        fcfg = (ctypes.c_float * 1)(self.bs.weights["bias"])
+        self.lib.call("avsr_beam_set_bias", self.handle, ctypes.cast(cfg, ctypes.c_void_p), ctypes.cast(fcfg, ctypes.c_void_p),
+                      *[t.data_ptr() for t in tabs])
+        self.bias_key, self.bias_keep = key, tabs  # (the tables stay alive as long as the session may read them)
 
     @staticmethod
     def _lm_weights(lm, lm_pe):
@@ -216,8 +248,8 @@ class NativeBeam:
                nws, maxlen, stream)
         n_out = ctypes.c_int(0)
         host_ptr, n_ptr = self.host.data_ptr(), ctypes.cast(ctypes.pointer(n_out), ctypes.c_void_p)
-        names = ["decoder"] + [k for k in ("lm", "length_bonus") if k in bs.full_scorers] + ["ctc"]
-        col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6}
+        names = ["decoder"] + [k for k in ("lm", "bias", "length_bonus") if k in bs.full_scorers] + ["ctc"]
+        col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6, "bias": 7}
         eos = bs.eos
         ended, best, best_len = [], -math.inf, {}
 
@@ -310,8 +342,8 @@ class NativeBeam:
         if yseq_host is None or yseq_host.shape[0] < rows * (Lmax + 2):
             yseq_host = self.group_yseq_host = torch.empty(rows * (Lmax + 2), dtype=torch.int64, pin_memory=pin)
         n_out = i32()
-        names = ["decoder"] + [k for k in ("lm", "length_bonus") if k in bs.full_scorers] + ["ctc"]
-        col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6}
+        names = ["decoder"] + [k for k in ("lm", "bias", "length_bonus") if k in bs.full_scorers] + ["ctc"]
+        col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6, "bias": 7}
         eos = bs.eos
         ended = [[] for _ in range(U)]
         best = [-math.inf] * U

@@ -41,6 +41,10 @@ def parse_args(argv=None):
     p.add_argument("--lm-conf", type=str, default=None,
                    help="JSON file with the language model's layer / unit / att_unit / head / embed_unit (default: 16 / 2048 / 512 / 8 / 128)")
     p.add_argument("--lm-weight", type=float, default=0.0, help="weight of the language model's log-probabilities (0: no fusion)")
+    p.add_argument("--bias-list", type=str, default=None, metavar="PATH",
+                   help="contextual biasing: a file with one expected phrase per line -- a line of integers is token ids, any other line "
+                        "is text (tokenised with the SentencePiece model); a boosted token must still be among the decoder's pre-beam candidates")
+    p.add_argument("--bias-weight", type=float, default=0.0, help="reward per matched token of a bias phrase, in log units (0: no biasing)")
     p.add_argument("--decode-mode", choices=["search", "rescore"], default="search",
                    help="search: the reference's label-synchronous hybrid CTC / attention beam search (default).  rescore: two-pass "
                         "decoding -- a CTC prefix beam search on the device, then one teacher-forced decoder (+ LM) pass over its n-best")
@@ -53,6 +57,8 @@ def parse_args(argv=None):
         p.error("--decode-batch and --decode-workers > 1 are two ways of decoding several utterances at once: choose one")
     if args.decode_batch > 1 and args.decode_mode == "rescore":
         p.error("--decode-batch groups the steps of the label-synchronous search: it does not apply to --decode-mode rescore")
+    if (args.bias_list or args.bias_weight) and args.decode_mode == "rescore":
+        p.error("--bias-list / --bias-weight bias the label-synchronous search: they do not apply to --decode-mode rescore")
     return args
 
 

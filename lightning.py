@@ -251,8 +251,12 @@ class ModelModule(_Base):
             def make(model, token_list, **kw):
                 return get_two_pass_decoder(model, token_list, beam_size=int(getattr(args, "rescore_beam", None) or 16),
                                             topk=int(getattr(args, "rescore_topk", None) or 16), **kw)
+        kw = {}
+        bias = self._bias_scorer()
+        if bias is not None:  # (parse_args refuses the flags together with --decode-mode rescore)
+            kw = dict(bias_phrases=bias, bias_weight=float(args.bias_weight))
         if not lm_path or lm_weight == 0.0:
-            return make(self.model, self.token_list)
+            return make(self.model, self.token_list, **kw)
         cached = getattr(self, "_lm", None)
         if cached is None or cached[0] != (lm_path, getattr(args, "lm_conf", None)):
             from auto_avsr_amd.lm import TransformerLM
@@ -260,7 +264,43 @@ class ModelModule(_Base):
             lm = TransformerLM.from_files(len(self.token_list), lm_path, getattr(args, "lm_conf", None),
                                           device=next(self.model.parameters()).device)
             cached = self._lm = ((lm_path, getattr(args, "lm_conf", None)), [lm])  # (in a list: not a sub-module, not in state_dict)
-        return make(self.model, self.token_list, rnnlm=cached[1][0], lm_weight=lm_weight)
+        return make(self.model, self.token_list, rnnlm=cached[1][0], lm_weight=lm_weight, **kw)
+
+    # ---- contextual biasing (not in the reference): a list of expected phrases boosted inside the beam search
+    def _bias_scorer(self):
+        """The ContextBiasScorer of this module (auto_avsr_amd/bias.py), None without a bias weight: created once from
+        `args.bias_list` (eval.py --bias-list: one phrase per line, a line of integers = token ids, any other line = text for
+        TextTransform.tokenize) with weight `args.bias_weight`, and kept across searches so that `set_bias` swaps its list in place."""
+        args = getattr(self, "args", None)
+        weight = float(getattr(args, "bias_weight", 0.0) or 0.0)
+        path = getattr(args, "bias_list", None)
+        if getattr(args, "decode_mode", "search") == "rescore":
+            return None
+        if weight == 0.0:
+            if path:
+                import warnings
+
+                warnings.warn(f"bias_list={path!r} without a bias weight (bias_weight is 0): the search runs without biasing")
+            return None
+        cached = getattr(self, "_bias", None)
+        if cached is None or cached[0] != path:
+            if not path:  # (legal: the list may come later through set_bias)
+                import warnings
+
+                warnings.warn(f"bias_weight={weight} without a bias list (bias_list is None): nothing is boosted until set_bias gives one")
+            from auto_avsr_amd.bias import ContextBiasScorer
+
+            phrases = read_bias_list(path, self.text_transform) if path else []
+            cached = self._bias = (path, ContextBiasScorer(phrases, len(self.token_list)))
+        return cached[1]
+
+    def set_bias(self, phrases):
+        """Replace the bias list (token-id phrases; [] = none) for the utterances decoded from now on, e.g. per utterance.  Needs a
+        bias weight (args.bias_weight); the running search object and its native sessions are kept, only the list is re-sent."""
+        sc = self._bias_scorer()
+        if sc is None:
+            raise ValueError("set_bias: no bias weight (args.bias_weight is 0 or missing): the search carries no bias scorer")
+        sc.set_phrases(phrases)
 
     def forward(self, sample):
         self.beam_search = self._make_beam_search()
@@ -285,6 +325,25 @@ class ModelModule(_Base):
         if HAVE_LIGHTNING:
             self.log("wer", wer)
         return wer
+
+
+def read_bias_list(path, text_transform=None):
+    """Phrases of a bias-list file: one per line, blank lines skipped; a line consisting only of integers is token ids, any other
+    line is text and goes through `text_transform.tokenize` (which needs the SentencePiece model file)."""
+    phrases = []
+    with open(path, encoding="utf8") as f:
+        for line in f:
+            parts = line.split()
+            if not parts:
+                continue
+            if all(p.lstrip("+-").isdigit() for p in parts):
+                phrases.append([int(p) for p in parts])
+                continue
+            if text_transform is None or getattr(text_transform, "spm", None) is None:
+                raise FileNotFoundError(f"{path}: the line {line.strip()!r} is text, but the SentencePiece model file of TextTransform "
+                                        "is missing; install it or give the phrases as token ids")
+            phrases.append([int(t) for t in text_transform.tokenize(line.strip())])
+    return phrases
 
 
 def _resolve_lm(model, token_list, rnnlm, rnnlm_conf, lm_weight, what="search"):
@@ -327,12 +386,15 @@ def get_two_pass_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty
 
 
 def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight=0.1, lm_weight=0.0,
-                            beam_size=40):
+                            beam_size=40, bias_phrases=None, bias_weight=0.0):
     """lightning.py:126-158: decoder (1 - ctc_weight) + CTC prefix scorer (ctc_weight) + length bonus (penalty), beam 40,
     pre-beam on the decoder scores.  No language model is shipped with the reference (`scorers["lm"] = None`); its `lm` slot is
     served here: rnnlm = an auto_avsr_amd.lm.TransformerLM, or the path of its state dict (ESPnet layout, optionally under a
     `predictor.` prefix) with rnnlm_conf = a dict or the path of a JSON file giving layer / unit / att_unit / head / embed_unit;
-    lm_weight = its weight in the score (shallow fusion).  lm_weight == 0 or rnnlm None: the search without a language model."""
+    lm_weight = its weight in the score (shallow fusion).  lm_weight == 0 or rnnlm None: the search without a language model.
+    Contextual biasing (not in the reference): bias_phrases = a list of phrases as token-id lists (or a ContextBiasScorer) puts an
+    auto_avsr_amd.bias.ContextBiasScorer into a `bias` slot after `lm`, bias_weight = its weight in log units per matched token.  A
+    boosted token still has to be among the decoder's pre-beam candidates.  bias_weight == 0 or bias_phrases None: no biasing."""
     from espnet.nets.batch_beam_search import BatchBeamSearch
     from espnet.nets.scorers.length_bonus import LengthBonus
 
@@ -352,10 +414,23 @@ def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, pena
         import warnings
 
         warnings.warn(f"lm_weight={lm_weight} without a language model (rnnlm is None): the search runs without fusion")
+    bias = None
+    if bias_phrases is not None and bias_weight != 0.0:
+        from auto_avsr_amd.bias import ContextBiasScorer
+
+        bias = bias_phrases if isinstance(bias_phrases, ContextBiasScorer) else ContextBiasScorer(bias_phrases, len(token_list))
+        if bias.n_vocab != len(token_list):
+            raise ValueError(f"the bias scorer's vocabulary ({bias.n_vocab}) is not the token list's ({len(token_list)})")
+    elif bias_weight != 0.0:
+        import warnings
+
+        warnings.warn(f"bias_weight={bias_weight} without a bias list (bias_phrases is None): the search runs without biasing")
     sos = eos = model.odim - 1
     scorers = model.scorers()
     scorers["lm"] = lm
+    scorers["bias"] = bias
     scorers["length_bonus"] = LengthBonus(len(token_list))
-    weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight, "length_bonus": penalty}
+    weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight, "bias": bias_weight if bias is not None else 0.0,
+               "length_bonus": penalty}
     return BatchBeamSearch(beam_size=beam_size, vocab_size=len(token_list), weights=weights, scorers=scorers, sos=sos, eos=eos,
                            token_list=token_list, pre_beam_score_key=None if ctc_weight == 1.0 else "decoder")

@@ -39,6 +39,10 @@ def main():
                     help="batched native search rows instead of the default ones: 16 utterances of T = 100 and of T = 400 frames through "
                          "BatchBeamSearch.forward_batch in groups of 1, 4, 8 and 16 beside one search at a time and forward_many(workers=4), "
                          "alternated, on the same encoder outputs (precise mode; python tools/bench_decode.py --batch > profiles/batch_decode.json)")
+    ap.add_argument("--bias", action="store_true",
+                    help="contextual-biasing rows instead of the default ones: a list of 1 000 random phrases of 2 - 5 tokens, weight 1.0 -- the "
+                         "native step without and with the list, alternated in the same run, and the python-issued step with the list "
+                         "(precise mode; python tools/bench_decode.py --bias > profiles/context_bias_decode.json)")
     ap.add_argument("--rescore-beam", type=int, default=16)
     ap.add_argument("--rescore-topk", type=int, default=16)
     ap.add_argument("--modes", type=str, default="precise", help="--two-pass: comma-separated numerical modes (eval.py decodes in precise)")
@@ -49,6 +53,8 @@ def main():
         return main_two_pass_sweep(args)
     if args.batch:
         return main_batch(args)
+    if args.bias:
+        return main_bias(args)
     if args.two_pass or args.two_pass_once:
         return main_two_pass(args)
     import lightning
@@ -413,6 +419,81 @@ def main_batch(args):
     print(json.dumps({"metric": "batched native hybrid CTC / attention beam search (one decoding step per group of U utterances) beside one search "
                                 "at a time and four sessions in flight, video E2E 250M, vocabulary 5049, search only (encoder outputs ready), wall "
                                 "clock between synchronisations, one warm-up then the sides alternated",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def main_bias(args):
+    import random
+    import statistics
+
+    import lightning
+    from synth import synth_batch, synth_state_dict
+
+    from auto_avsr_amd import decoding
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode.py --bias needs an MI355X: there is nothing to time without one")
+    dev = torch.device("cuda:0")
+    V = 5049
+    m = E2E(V, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    toks = [str(i) for i in range(V)]
+    rng = random.Random(11)
+    phrases = [[rng.randint(1, V - 2) for _ in range(rng.randint(2, 5))] for _ in range(1000)]
+    w_bias = 1.0
+    AF.set_mode("precise")
+    rows = []
+    for T in (100, 400):
+        x, _, _ = synth_batch("video", 1, T, 3, V, seed=T, lengths=[T])
+        with torch.no_grad():
+            enc = m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float()
+        plain = lightning.get_beam_search_decoder(m, toks, beam_size=args.beam)
+        decoding.NATIVE_BEAM = True
+        with torch.no_grad():
+            first = plain(enc)[0].asdict()["yseq"][1:-1]
+        # random phrases never meet a hypothesis: a few cut out of the unbiased winner make the list matter (the rest is its bulk)
+        hot = [first[i: i + 3] for i in range(0, max(1, len(first) - 3), 7)]
+        hot = [p for p in hot if p and all(1 <= t <= V - 2 for t in p)]
+        with_list = {"native_bias": lightning.get_beam_search_decoder(m, toks, beam_size=args.beam, bias_phrases=phrases + hot, bias_weight=w_bias),
+                     "python_bias": lightning.get_beam_search_decoder(m, toks, beam_size=args.beam, bias_phrases=phrases + hot, bias_weight=w_bias)}
+        sides = {"native_no_list": (plain, True), "native_bias": (with_list["native_bias"], True), "python_bias": (with_list["python_bias"], False)}
+        times, out = {k: [] for k in sides}, {}
+        for rep_ in range(args.reps + 1):  # first repetition = warm-up; the sides alternate within a repetition
+            for k, (bs, native) in sides.items():
+                decoding.NATIVE_BEAM = native
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                with torch.no_grad():
+                    out[k] = bs(enc)
+                torch.cuda.synchronize()
+                if rep_:
+                    times[k].append((time.perf_counter() - t0) * 1e3)
+                assert bool(bs._native) == native
+        sc = with_list["native_bias"].full_scorers["bias"]
+        row = {"T_frames": T, "beam": args.beam, "mode": "precise", "vocabulary": V, "bias_weight": w_bias, "phrases": len(sc.phrases),
+               "trie_nodes": sc.n_nodes, "trie_edges": sc.n_edges, "root_fan_out": int(sc.first[1]), "repetitions": args.reps, "sides": {}}
+        for k in sides:
+            steps = max(len(h.asdict()["yseq"]) for h in out[k]) - 1
+            med = statistics.median(times[k])
+            row["sides"][k] = {"beam_search_ms": {"median": round(med, 2), "min": round(min(times[k]), 2), "max": round(max(times[k]), 2)},
+                               "longest_hypothesis_tokens": steps, "ms_per_token": round(med / max(steps, 1), 4),
+                               "best_bias_sum": out[k][0].asdict()["scores"].get("bias")}
+        a, b = row["sides"]["native_no_list"]["ms_per_token"], row["sides"]["native_bias"]["ms_per_token"]
+        row["list_cost_ms_per_token"] = round(b - a, 4)
+        row["list_cost_relative"] = round(b / a - 1.0, 4)
+        row["native_and_python_step_agree_on_best"] = out["native_bias"][0].asdict()["yseq"] == out["python_bias"][0].asdict()["yseq"]
+        row["list_changes_best"] = out["native_bias"][0].asdict()["yseq"] != out["native_no_list"][0].asdict()["yseq"]
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    AF.set_mode("bf16")
+    decoding.NATIVE_BEAM = True
+    print(json.dumps({"metric": "contextual biasing in the hybrid CTC / attention beam search: native one-call step without and with a list of "
+                                "1 000 random 2 - 5-token phrases (plus a few cut out of the unbiased winner), and the python-issued step with it; video "
+                                "E2E 250M decoder, search only (encoder output ready), wall clock between synchronisations, one warm-up then "
+                                "the sides alternated",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
 
 
