@@ -21,6 +21,13 @@
 //       (parent node, token) record in the workspace; with the per-frame beam records (node, length, pb, pnb) and the token
 //       sets these are the history from which the host can replay every frame -- all of it plain stores that nothing waits for.
 //       The n-best token sequences are read back from the node records at the end (len(prefix) steps per hypothesis).
+//   avsr_ctc_beam_search_bias   the same search with a list of boosted phrases (the trie of auto_avsr_amd/bias.py, its rules 1 to 3):
+//       ctc_beam_kernel<true>.  Every beam entry also carries its trie node and its running sum of gains -- functions of the prefix'
+//       tokens alone, so a staying candidate keeps them and the merge of P1 needs no new case -- and P3 ranks by total + weight *
+//       sum; the masses of the recursion and every stored record stay pure CTC.  Lookups from the ROOT (rule 1 at the root, the retry
+//       of rule 2) depend on the frame's tokens only: ctc_root_child_kernel resolves them off the chain, one binary search per (b, t,
+//       k) among the root's children, and the search stages the result with the token rows.  Only an entry that stands at a
+//       non-root node reads the tables inside the frame loop (P1: its unc; P2: its own edges, for the live extensions).
 //   avsr_ctc_score   N label sequences per utterance against one [T][V] matrix of log-posteriors: label builder of ctc_common.h
 //       per sequence, a gather of the 2L+1 extended-label columns, and the alpha recursion of the loss (one wave per sequence).
 #include "prims.h"
@@ -33,6 +40,7 @@ constexpr int CB_MAXW = 64, CB_MAXK = 32;
 constexpr int CB_MAXC = CB_MAXW * (CB_MAXK + 1);  // candidates of a frame
 constexpr int CB_FCH = 8;                         // frames per staged chunk of (token, lp) rows
 constexpr int CB_STG = 3;                         // registers per thread that hold the next chunk: 8 * 65 words <= 3 * 256
+constexpr int CB_STG_BIAS = 4;                    // ... with the root children of the tokens: 8 * 97 words <= 4 * 256
 constexpr int CB_NT_MIN = 256, CB_NT_MAX = 1024;  // threads of the search's block
 constexpr int TK_NT = 256;
 
@@ -129,6 +137,29 @@ __global__ __launch_bounds__(TK_NT) void ctc_topk_kernel(const float* __restrict
     }
 }
 
+// ---- contextual biasing: per (utterance, frame, token slot) the root's child on that token, -1 if the root has no such edge
+__global__ __launch_bounds__(256) void ctc_root_child_kernel(const int32_t* __restrict__ tok, const int64_t* __restrict__ in_lens,
+                                                             const int32_t* __restrict__ b_first, const int32_t* __restrict__ b_tok,
+                                                             const int32_t* __restrict__ b_child, int K, int Tlen, long total,
+                                                             int32_t* __restrict__ rootc) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long row = i / K;
+    if ((int64_t)(row % Tlen) >= in_lens[row / Tlen]) return;  // (no token set was written for this frame)
+    const int v = tok[i];
+    int lo = b_first[0], hi = b_first[1], found = -1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1, x = b_tok[mid];
+        if (x == v) {
+            found = b_child[mid];
+            break;
+        }
+        if (x < v) lo = mid + 1;
+        else hi = mid;
+    }
+    rootc[i] = found;
+}
+
 struct BeamArgs {
     const int32_t* tok;  // [B][T][K]
     const float* val;    // [B][T][K]
@@ -141,9 +172,28 @@ struct BeamArgs {
     float *score, *pb, *pnb;
     int W, K, nbest, T;
 };
+struct BeamArgsBias : BeamArgs {  // contextual biasing: what ctc_beam_kernel<true> takes on top
+    const int32_t* rootc;  // [B][T][K]
+    const int32_t *b_first, *b_tok, *b_child, *b_unc;
+    float b_weight;
+    float* bias_sum;     // [B][nbest]
+    int32_t* bias_node;  // [B][nbest]
+};
+template <bool BIAS>
+struct BeamArgsOf {
+    typedef BeamArgs type;
+};
+template <>
+struct BeamArgsOf<true> {
+    typedef BeamArgsBias type;
+};
+
+// a candidate's bias step in one word: the node reached (< 2^24 = AVSR_BIAS_MAX_NODES), +1 taken, unc of the parent's node taken back
+constexpr int CB_BIAS_PLUS = 1 << 24, CB_BIAS_BACK = 1 << 25, CB_BIAS_NODE = (1 << 24) - 1;
 
 // ---- one workgroup per utterance walks its frames
-__global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
+template <bool BIAS>
+__global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf<BIAS>::type a) {
     // the beam, double buffered: hash of the prefix and of its parent prefix, last token, length, node id, pb, pnb, total
     __shared__ uint64_t s_h[2][CB_MAXW], s_hp[2][CB_MAXW];
     __shared__ int s_last[2][CB_MAXW], s_len[2][CB_MAXW], s_node[2][CB_MAXW];
@@ -155,9 +205,14 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
     __shared__ float s_cpnb[CB_MAXC], s_cpb[CB_MAXW];
     __shared__ int s_rank[CB_MAXC];  // candidates that beat candidate s, summed over the parts of the block
     __shared__ int s_live;           // candidates of the frame that carry mass
-    __shared__ int s_stage[2][CB_FCH * (2 * CB_MAXK + 1)];  // per frame of a chunk: K tokens, K values, the blank's value
+    // per frame of a chunk: K tokens, K values, the blank's value (BIAS: and the K root children of the tokens)
+    __shared__ int s_stage[2][CB_FCH * ((BIAS ? 3 : 2) * CB_MAXK + 1)];
+    // BIAS: trie node and sum of gains of the beam's entries, unc of the current entries' nodes, the candidates' packed steps
+    __shared__ int s_bn[2][BIAS ? CB_MAXW : 1], s_bg[2][BIAS ? CB_MAXW : 1], s_bu[BIAS ? CB_MAXW : 1];
+    __shared__ int s_cb[BIAS ? CB_MAXW * CB_MAXK : 1];
+    constexpr int STG = BIAS ? CB_STG_BIAS : CB_STG;
     const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
-    const int W = a.W, K = a.K, T = a.T, K1 = K + 1, RW = 2 * K + 1;
+    const int W = a.W, K = a.K, T = a.T, K1 = K + 1, RW = (BIAS ? 3 : 2) * K + 1;
     // P3: the block is `parts` groups of Cw threads (whole waves); group g compares every candidate with its share of the others
     const int Cw = (W * K1 + 63) / 64 * 64, parts = Cw <= NT ? NT / Cw : 1;
     const int part = parts > 1 ? tid / Cw : 0, s_first = parts > 1 ? tid - part * Cw : tid, s_step = parts > 1 ? Cw : NT;
@@ -169,8 +224,14 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
     int32_t* g_cnt = a.cnt + (long)b * T;
     int32_t* g_node = a.node + (long)b * ((long)T * W + 1) * 2;
     int32_t* g_beam = a.beam + (long)b * T * W * 4;
+    const int32_t* g_root = nullptr;
+    if constexpr (BIAS) g_root = a.rootc + (long)b * T * K;
 
     if (tid == 0) {
+        if constexpr (BIAS) {
+            s_bn[0][0] = 0;
+            s_bg[0][0] = 0;
+        }
         s_h[0][0] = CB_ROOT_HASH;
         s_hp[0][0] = CB_NO_PARENT;
         s_last[0][0] = -1;
@@ -188,23 +249,24 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
     for (int i = tid; i < CB_MAXW * CB_MAXK; i += NT) s_kill[i] = 0;
 
     // staging of the token rows: chunk c = frames [c * FCH, (c + 1) * FCH), word w = f * RW + x of a chunk
-    int pre[CB_STG];
+    int pre[STG];
     auto fetch = [&](int chunk) {
 #pragma unroll
-        for (int q = 0; q < CB_STG; q++) {
+        for (int q = 0; q < STG; q++) {
             const int w = tid + q * NT, f = w / RW, x = w - f * RW, t = chunk * CB_FCH + f;
             int v = 0;
             if (f < CB_FCH && t < Tb) {
                 if (x < K) v = g_tok[(long)t * K + x];
                 else if (x < 2 * K) v = __builtin_bit_cast(int, g_val[(long)t * K + x - K]);
-                else v = __builtin_bit_cast(int, g_blk[t]);
+                else if (!BIAS || x == 2 * K) v = __builtin_bit_cast(int, g_blk[t]);
+                else v = g_root[(long)t * K + x - 2 * K - 1];
             }
             pre[q] = v;
         }
     };
     auto stash = [&](int buf) {
 #pragma unroll
-        for (int q = 0; q < CB_STG; q++) {
+        for (int q = 0; q < STG; q++) {
             const int w = tid + q * NT;
             if (w < CB_FCH * RW) s_stage[buf][w] = pre[q];
         }
@@ -220,6 +282,7 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
         const int* st_tok = &s_stage[chunk & 1][f * RW];
         const float* st_val = reinterpret_cast<const float*>(st_tok + K);
         const float lpb = st_val[K];
+        const int* st_root = st_tok + 2 * K + 1;  // (BIAS only)
         const int n = s_n[cur], nxt = cur ^ 1, N = n * K1, stamp = t + 1;
         // ---- P1: parent slots, token slots of the last tokens, merged extensions
         for (int p = tid; p < n * n; p += NT) {
@@ -239,6 +302,8 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
             s_n[nxt] = 0;
             s_live = 0;
         }
+        if constexpr (BIAS)  // what a mismatch at entry i takes back: the one table read of an entry that does not stand at the root
+            for (int i = tid; i < n; i += NT) s_bu[i] = s_bn[cur][i] ? a.b_unc[s_bn[cur][i]] : 0;
         lds_barrier();
         // ---- P2: the candidates.  Slot i * (K + 1) + k: entry i extended by token k (k < K) or staying (k == K)
         int alive = 0;
@@ -261,6 +326,30 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
                 v = (st_tok[k] != s_last[cur][i] ? s_tot[cur][i] : s_pb[cur][i]) + st_val[k];
                 if (s_kill[i * K + k] == stamp) v = neg_inf();
                 s_cpnb[s] = v;
+            }
+            if constexpr (BIAS) {  // the ranking key: total + weight * (sum of gains of the candidate's prefix); a dead candidate stays dead
+                int g = s_bg[cur][i];
+                if (k < K && v > neg_inf()) {
+                    const int sn = s_bn[cur][i], rc = st_root[k];
+                    int step = -1;
+                    if (sn != 0) {  // rule 1 below the root: binary search among the node's own edges
+                        const int c = st_tok[k];
+                        int lo = a.b_first[sn], hi = a.b_first[sn + 1];
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1, x = a.b_tok[mid];
+                            if (x == c) {
+                                step = a.b_child[mid] | CB_BIAS_PLUS;
+                                break;
+                            }
+                            if (x < c) lo = mid + 1;
+                            else hi = mid;
+                        }
+                    }
+                    if (step < 0) step = (sn != 0 ? CB_BIAS_BACK : 0) | (rc >= 0 ? rc | CB_BIAS_PLUS : 0);  // rule 2 (at the root: rule 1)
+                    s_cb[i * K + k] = step;
+                    g += ((step & CB_BIAS_PLUS) != 0) - ((step & CB_BIAS_BACK) ? s_bu[i] : 0);
+                }
+                v += a.b_weight * (float)g;
             }
             s_cv[s] = v;
             s_rank[s] = 0;
@@ -305,11 +394,17 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
         }
         lds_barrier();
         for (int s = tid; s < N; s += NT) {
-            const float v = s_cv[s];
+            float v = s_cv[s];
             if (!(v > neg_inf())) continue;
             const int rank = s_rank[s], live = s_live;
             if (rank >= W) continue;
             const int i = s / K1, k = s - i * K1, r = rank;
+            if constexpr (BIAS) {  // the pure CTC total, as P2 computed it, and the bias state of the prefix
+                v = k == K ? lse2(s_cpb[i], s_cpnb[s]) : s_cpnb[s];
+                const int step = k == K ? 0 : s_cb[i * K + k];
+                s_bn[nxt][r] = k == K ? s_bn[cur][i] : step & CB_BIAS_NODE;
+                s_bg[nxt][r] = s_bg[cur][i] + ((step & CB_BIAS_PLUS) != 0) - ((step & CB_BIAS_BACK) ? s_bu[i] : 0);
+            }
             int node = s_node[cur][i], len = s_len[cur][i];
             float pbn = neg_inf();
             if (k == K) {
@@ -379,6 +474,10 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(BeamArgs a) {
         a.score[(long)b * nbest + r] = ok ? s_tot[cur][r] : neg_inf();
         a.pb[(long)b * nbest + r] = ok ? s_pb[cur][r] : neg_inf();
         a.pnb[(long)b * nbest + r] = ok ? s_pnb[cur][r] : neg_inf();
+        if constexpr (BIAS) {  // <eos> is never in the trie: it takes the uncommitted part back
+            a.bias_sum[(long)b * nbest + r] = ok ? (float)(s_bg[cur][r] - a.b_unc[s_bn[cur][r]]) : 0.f;
+            a.bias_node[(long)b * nbest + r] = ok ? s_bn[cur][r] : 0;
+        }
         if (ok) {
             int node = s_node[cur][r];
             for (int i = s_len[cur][r] - 1; i >= 0 && node > 0; i--) {
@@ -474,6 +573,21 @@ __global__ __launch_bounds__(64) void ctc_score_alpha_kernel(const float* __rest
 
 int64_t align16(int64_t x) { return (x + 15) / 16 * 16; }
 
+struct BiasList {  // what avsr_ctc_beam_search_bias adds to the plain call
+    const int32_t *first, *tok, *child, *unc;
+    float weight;
+    float* sum;
+    int32_t* node;
+};
+
+__global__ __launch_bounds__(256) void ctc_bias_zero_kernel(float* __restrict__ bias_sum, int32_t* __restrict__ bias_node, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        bias_sum[i] = 0.f;
+        bias_node[i] = 0;
+    }
+}
+
 }  // namespace
 
 // Workspace layout (header): tok | val | blk | cnt | node | (to 16 bytes) beam
@@ -487,9 +601,10 @@ extern "C" int64_t avsr_ctc_beam_workspace_bytes(int B, int T, int W, int K) {
     return beam_rec_offset(B, T, W, K) + (int64_t)B * T * W * 16;
 }
 
-extern "C" int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
-                                    int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid,
-                                    void* workspace, int B, int T, int V, hipStream_t stream) {
+// the plain search (bias == nullptr) or the search with a bias list, whose root-child table follows the plain layout
+static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest, int32_t* tokens,
+                       int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid, void* workspace, int B, int T, int V,
+                       hipStream_t stream, const BiasList* bias) {
     AVSR_REQUIRE(W >= 2 && W <= CB_MAXW, "ctc_beam_search: beam must be 2 .. 64");
     AVSR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V - 1, "ctc_beam_search: token budget must be 1 .. min(32, V - 1)");
     AVSR_REQUIRE(nbest >= 1 && nbest <= W, "ctc_beam_search: nbest must be 1 .. beam");
@@ -498,7 +613,7 @@ extern "C" int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* 
     AVSR_REQUIRE(T >= 1 && (int64_t)T * W < (1 << 30), "ctc_beam_search: 1 .. 2^30 / beam frames");
     AVSR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_beam_search: workspace must be 16-byte aligned");
     if (B <= 0) return 0;
-    BeamArgs a;
+    BeamArgsBias a;
     int32_t* tok = reinterpret_cast<int32_t*>(workspace);
     float* val = reinterpret_cast<float*>(tok + (int64_t)B * T * K);
     float* blk = val + (int64_t)B * T * K;
@@ -524,9 +639,56 @@ extern "C" int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* 
     // four threads per candidate where a block can hold them (the rank loop of P3 is the longest stretch of a frame), whole waves
     int nt = (W * (K + 1) + 63) / 64 * 64 * 4;
     nt = nt < CB_NT_MIN ? CB_NT_MIN : (nt > CB_NT_MAX ? CB_NT_MAX : nt);
-    AVSR_LAUNCH(ctc_beam_kernel, dim3(B), dim3(nt), 0, stream, a);
+    if (bias == nullptr) {
+        AVSR_LAUNCH(ctc_beam_kernel<false>, dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgs&>(a));
+    } else {
+        int32_t* rootc = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + avsr_ctc_beam_workspace_bytes(B, T, W, K));
+        a.rootc = rootc;
+        a.b_first = bias->first;
+        a.b_tok = bias->tok;
+        a.b_child = bias->child;
+        a.b_unc = bias->unc;
+        a.b_weight = bias->weight;
+        a.bias_sum = bias->sum;
+        a.bias_node = bias->node;
+        const long total = (long)B * T * K;
+        AVSR_LAUNCH(ctc_root_child_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tok, in_lens, a.b_first, a.b_tok,
+                    a.b_child, K, T, total, rootc);
+        AVSR_LAUNCH(ctc_beam_kernel<true>, dim3(B), dim3(nt), 0, stream, a);
+    }
     AVSR_CHECK_LAUNCH("ctc_beam_search");
     return 0;
+}
+
+extern "C" int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
+                                    int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid,
+                                    void* workspace, int B, int T, int V, hipStream_t stream) {
+    return beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, nullptr);
+}
+
+extern "C" int64_t avsr_ctc_beam_bias_workspace_bytes(int B, int T, int W, int K) {
+    if (B <= 0 || T <= 0 || W <= 0 || K <= 0) return 16;
+    return avsr_ctc_beam_workspace_bytes(B, T, W, K) + align16((int64_t)B * T * K * 4);
+}
+
+extern "C" int avsr_ctc_beam_search_bias(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
+                                         const int32_t* first, const int32_t* tok, const int32_t* child, const int32_t* unc, int n_nodes,
+                                         int n_edges, float weight, int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb,
+                                         int32_t* n_valid, float* bias_sum, int32_t* bias_node, void* workspace, int B, int T, int V,
+                                         hipStream_t stream) {
+    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_BIAS_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_BIAS_MAX_EDGES,
+                 "ctc_beam_search_bias: too many nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
+    AVSR_REQUIRE(weight == weight && fabsf(weight) <= 1e30f, "ctc_beam_search_bias: the weight must be finite");
+    if (n_nodes == 0 || n_edges == 0) {  // no list: the plain search, and nothing was boosted
+        const int rc = beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream,
+                                   nullptr);
+        if (rc != 0 || B <= 0) return rc;
+        AVSR_LAUNCH(ctc_bias_zero_kernel, dim3((unsigned)((B * nbest + 255) / 256)), dim3(256), 0, stream, bias_sum, bias_node, B * nbest);
+        AVSR_CHECK_LAUNCH("ctc_beam_search_bias");
+        return 0;
+    }
+    const BiasList bias = {first, tok, child, unc, weight, bias_sum, bias_node};
+    return beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, &bias);
 }
 
 // Workspace layout: lpg[B*N*T*Smax] f32 | ext[B*N*Smax] i32 | lens[B*N] i32

@@ -570,24 +570,52 @@ def ctc_align(logits, ld, labels, in_lens, B, T, V, blank=0, ignore_id=-1):
     return ali, score
 
 
-def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=None):
+_ZERO = {}
+
+
+def _zeros_view(shape, dtype, dev):
+    """Read-only zeros of any shape without a launch: a stride-0 view of one cached element per (device, dtype)."""
+    z = _ZERO.get((str(dev), dtype))
+    if z is None:
+        z = _ZERO[(str(dev), dtype)] = torch.zeros(1, dtype=dtype, device=dev)
+    return z.expand(shape)
+
+
+def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=None, bias=None, bias_weight=0.0):
     """CTC prefix beam search (csrc/ctc_beam.hip).  lp: f32 [B*T, ld] log-posteriors; in_lens int64 [B].  Returns a dict of
     device tensors: tokens int32 [B, nbest, T] (-1 padded), lens int32 [B, nbest], score / pb / pnb f32 [B, nbest], n_valid int32
     [B], and the history of the search as views of its workspace (ctc_beam_trace rebuilds the per-frame beams from them):
     topk_tok int32 / topk_val f32 [B, T, K], blank_val f32 [B, T], count int32 [B, T], node int32 [B, T*W+1, 2] (parent, token),
-    slots int32 [B, T, W, 4] (node id, length, pb bits, pnb bits).  Rows t >= in_lens[b] of the history are not written."""
+    slots int32 [B, T, W, 4] (node id, length, pb bits, pnb bits).  Rows t >= in_lens[b] of the history are not written.
+    bias (an auto_avsr_amd.bias.ContextBiasScorer) with bias_weight != 0: contextual biasing, avsr_ctc_beam_search_bias -- a frame
+    keeps the prefixes of largest total + bias_weight * (sum of the prefix' gains); every mass above stays pure CTC.  The dict always
+    carries bias_sum f32 [B, nbest] (the gains a finished hypothesis keeps) and bias_node int32 [B, nbest]; bias None or bias_weight 0
+    is the plain call, with the launches it always had: the two are then read-only zeros (stride-0 views, no fill is launched)."""
     W, K = int(beam), int(topk)
     nbest = W if nbest is None else int(nbest)
     dev = lp.device
-    ws_bytes = call("avsr_ctc_beam_workspace_bytes", B, T, W, K)
+    biased = bias is not None and float(bias_weight) != 0.0
+    ws_bytes = call("avsr_ctc_beam_bias_workspace_bytes" if biased else "avsr_ctc_beam_workspace_bytes", B, T, W, K)
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
     tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
     lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
     n_valid = torch.empty(B, dtype=torch.int32, device=dev)
     score, pb, pnb = (torch.empty(B, nbest, dtype=torch.float32, device=dev) for _ in range(3))
-    call("avsr_ctc_beam_search", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, _ptr(tokens), _ptr(lens), _ptr(score),
-         _ptr(pb), _ptr(pnb), _ptr(n_valid), _ptr(ws), B, T, V, _stream(lp))
-    out = {"tokens": tokens, "lens": lens, "score": score, "pb": pb, "pnb": pnb, "n_valid": n_valid, "beam": W, "topk": K}
+    if biased:
+        if bias.n_vocab != V:
+            raise ValueError(f"ctc_beam_search: the bias scorer's vocabulary ({bias.n_vocab}) is not the posteriors' ({V})")
+        bias_sum = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+        bias_node = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+        tabs = bias.device_tables(dev)  # (the scorer keeps them alive)
+        call("avsr_ctc_beam_search_bias", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, *[_ptr(t) for t in tabs],
+             bias.n_nodes, bias.n_edges, float(bias_weight), _ptr(tokens), _ptr(lens), _ptr(score), _ptr(pb), _ptr(pnb), _ptr(n_valid),
+             _ptr(bias_sum), _ptr(bias_node), _ptr(ws), B, T, V, _stream(lp))
+    else:
+        bias_sum, bias_node = _zeros_view((B, nbest), torch.float32, dev), _zeros_view((B, nbest), torch.int32, dev)
+        call("avsr_ctc_beam_search", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, _ptr(tokens), _ptr(lens), _ptr(score),
+             _ptr(pb), _ptr(pnb), _ptr(n_valid), _ptr(ws), B, T, V, _stream(lp))
+    out = {"tokens": tokens, "lens": lens, "score": score, "pb": pb, "pnb": pnb, "n_valid": n_valid, "beam": W, "topk": K,
+           "bias_sum": bias_sum, "bias_node": bias_node}
     if T > 0:
         o = 0
         for name, shape, as_f32 in (("topk_tok", (B, T, K), False), ("topk_val", (B, T, K), True), ("blank_val", (B, T), True),

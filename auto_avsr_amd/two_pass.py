@@ -4,12 +4,18 @@ language model, when there is one -- over all of them rescores it under the obje
 
     score(y) = (1 - ctc_weight) * sum_{i <= L+1} log p_dec(y_i | sos, y_<i)  +  ctc_weight * log P_ctc(y | x)
                + lm_weight * sum_{i <= L+1} log p_lm(y_i | sos, y_<i)  +  penalty * (L + 1),        y_{L+1} = <eos>
+               + bias_weight * (gains of auto_avsr_amd/bias.py along y_1 .. y_{L+1})
 
 which is exactly what the reference's BatchBeamSearch stores for a hypothesis that ended with a scored <eos> (its `scores`: the
 teacher-forced decoder sum, the exact CTC log-likelihood, len(y) + 1 for the length bonus; tests/test_two_pass.py pins this on the
 golden searches).  The first-pass score only selects the n-best; the CTC term of the final score is the exact likelihood
 (avsr_ctc_score: all hypotheses of an utterance against one copy of its posteriors).  The label-synchronous search is a chain of
-maxlen dependent decoder steps per utterance; here the only chain is the T frames inside one kernel."""
+maxlen dependent decoder steps per utterance; here the only chain is the T frames inside one kernel.
+
+Contextual biasing (`scorers["bias"]`, a ContextBiasScorer, with `weights["bias"]`): the first pass ranks its prefixes by CTC total +
+weight * (gains so far), which pulls the expected phrases into the beam (a boosted token still has to be among the frame's `topk`
+tokens), and the objective carries the bias term of the label-synchronous search; the term of the n-best comes back from the first
+pass itself.  The scorer is read at every call: `set_phrases` between utterances needs no rebuild."""
 from typing import List
 
 import torch
@@ -22,7 +28,7 @@ from .decoding import Hypothesis
 class TwoPassDecoder:
     """A plain object (it owns no parameters: the scorers stay where they are).  Drop-in for BatchBeamSearch where it is called
     (`__call__(enc)`, `forward_many(encs)`): the same scorer / weight dictionaries as lightning.get_beam_search_decoder builds -- `decoder` (TransformerDecoder), `ctc` (the CTC head or its CTCPrefixScorer),
-    optional `lm` (TransformerLM), optional `length_bonus` (only its weight is used) -- and lists of decoding.Hypothesis, best first,
+    optional `lm` (TransformerLM), optional `bias` (ContextBiasScorer), optional `length_bonus` (only its weight is used) -- and lists of decoding.Hypothesis, best first,
     with yseq = [sos, y..., eos] and one `scores` entry per scorer of non-zero weight."""
 
     def __init__(self, scorers, weights, sos, eos, token_list=None, beam_size=16, topk=16, nbest=None, blank=0, ignore_id=-1):
@@ -34,11 +40,17 @@ class TwoPassDecoder:
         self.ctc = getattr(ctc, "ctc", ctc)  # (CTCPrefixScorer wraps the head)
         self.decoder = scorers["decoder"]
         self.lm = self.scorers.get("lm")
+        self.bias = self.scorers.get("bias")
         if self.lm is not None and not hasattr(self.lm, "att_unit"):
             raise TypeError("lm: an auto_avsr_amd.lm.TransformerLM")
         self.sos, self.eos, self.blank, self.ignore_id = int(sos), int(eos), int(blank), int(ignore_id)
         self.token_list = token_list
         self.n_vocab = self.ctc.ctc_lo.out_features
+        if self.bias is not None:  # contextual biasing: this build's trie scorer, nothing else in that slot
+            from .bias import ContextBiasScorer
+
+            if not isinstance(self.bias, ContextBiasScorer) or self.bias.n_vocab != self.n_vocab:
+                raise TypeError(f"bias: an auto_avsr_amd.bias.ContextBiasScorer over the CTC head's vocabulary ({self.n_vocab})")
         self.beam_size, self.topk = int(beam_size), min(int(topk), self.n_vocab - 1)
         self.nbest = self.beam_size if nbest is None else int(nbest)
         self.last_first_pass = None  # the first pass' result of the latest call (tools / tests)
@@ -52,7 +64,8 @@ class TwoPassDecoder:
 
     def first_pass(self, lp, hlens):
         """The n-best prefixes per utterance as label rows padded with ignore_id: (labels int64 [B, N, Lmax], n_valid list)."""
-        res = AF.ctc_beam_search(lp, hlens, blank=self.blank, beam=self.beam_size, topk=self.topk, nbest=self.nbest)
+        res = AF.ctc_beam_search(lp, hlens, blank=self.blank, beam=self.beam_size, topk=self.topk, nbest=self.nbest, bias=self.bias,
+                                 bias_weight=self.weights.get("bias", 0.0))
         self.last_first_pass = res
         Lmax = max(1, int(res["lens"].max()))
         return res["tokens"][:, :, :Lmax].to(torch.int64).contiguous(), res["n_valid"].tolist()
@@ -67,9 +80,18 @@ class TwoPassDecoder:
         nll, _, _ = ops.ce_smooth(pit[0], pit[1], ys_out.reshape(-1).contiguous(), V, 0.0, want_grad=False, ignore_id=self.ignore_id)
         return -nll.view(R, L).sum(1)
 
-    def score_labels(self, memory, hlens, lp, labels):
+    def _bias_sums(self, labels):
+        """The bias term of labels [B, N, Lmax] on the host: the gains along each row and of its <eos>."""
+        rows = []
+        for row in labels.reshape(-1, labels.shape[-1]).tolist():
+            g, s = self.bias.walk([t for t in row if t != self.ignore_id])
+            rows.append(float(g + self.bias.step(s, self.eos)[0]))
+        return torch.tensor(rows, dtype=torch.float32).view(labels.shape[:2]).to(labels.device)
+
+    def score_labels(self, memory, hlens, lp, labels, bias_sum=None):
         """The terms of the objective for labels [B, N, Lmax] (padded with ignore_id) of the utterances memory [B, T, D]: a dict of
-        [B, N] tensors -- `score` and one entry per scorer of non-zero weight."""
+        [B, N] tensors -- `score` and one entry per scorer of non-zero weight.  bias_sum [B, N]: the bias term where the first pass
+        already has it; None: walked on the host."""
         B, N, Lmax = labels.shape
         dev = memory.device
         out = {}
@@ -87,8 +109,10 @@ class TwoPassDecoder:
             out["lm"] = self._token_sums(self.lm(ys_in)[..., : self.n_vocab], ys_out).view(B, N)
         if self.weights.get("length_bonus", 0.0) != 0.0:
             out["length_bonus"] = n_tok
+        if self.bias is not None:
+            out["bias"] = self._bias_sums(labels) if bias_sum is None else bias_sum.to(torch.float32)
         total = torch.zeros(B, N, dtype=torch.float32, device=dev)
-        for k in ("decoder", "lm", "length_bonus", "ctc"):
+        for k in ("decoder", "lm", "bias", "length_bonus", "ctc"):
             if k in out:
                 total = total + self.weights[k] * out[k]
         out["score"] = total
@@ -135,7 +159,7 @@ class TwoPassDecoder:
             return []
         memory, hlens, lp = self._posteriors(xs)
         labels, n_valid = self.first_pass(lp, hlens)
-        terms = self.score_labels(memory, hlens, lp, labels)
+        terms = self.score_labels(memory, hlens, lp, labels, bias_sum=self.last_first_pass["bias_sum"] if self.bias is not None else None)
         labels = labels.cpu()
         terms = {k: v.cpu() for k, v in terms.items()}
         return [self._hypotheses(labels, terms, b, max(1, int(n_valid[b]))) for b in range(len(xs))]

@@ -280,6 +280,26 @@ int64_t avsr_ctc_beam_workspace_bytes(int B, int T, int W, int K);
 int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest, int32_t* tokens,
                          int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid, void* workspace, int B, int T,
                          int V, avsr_stream_t stream);
+/* The same search with contextual biasing (a list of boosted phrases; the tables and lookup rules of avsr_bias_score /
+ * avsr_beam_set_bias below: first [n_nodes + 1], tok / child [n_edges], unc [n_nodes], int32 device tables owned by the caller that
+ * outlive the call; ONE list for all utterances of the launch).  Every beam entry carries the trie node of its prefix and the running
+ * sum of its gains (+1 along an edge of the node; otherwise -unc[node] and the token alone is retried from the root; no failure
+ * links), and a frame keeps the W prefixes of largest logaddexp(pb, pnb) + weight * sum.  Nothing else sees the bias: pb / pnb of the
+ * recursion, score / pb / pnb of the outputs and the beam records of the workspace stay pure CTC masses, a prefix without mass stays
+ * dead, and a boosted token still has to be among the frame's K tokens.  The n-best is the last beam in its (biased) order; beside the
+ * outputs of the plain search it returns bias_sum f32 [B][nbest] = sum - unc[node], the gains a finished hypothesis keeps (<eos> is
+ * never in the trie and takes the uncommitted part back), and bias_node int32 [B][nbest]; both 0 beyond n_valid[b].  The workspace
+ * (avsr_ctc_beam_bias_workspace_bytes, 16-byte aligned) is the plain layout followed by
+ *   rootc int32 [B][T][K]  the root's child on each of the frame's tokens, -1 without such an edge (resolved by a launch of its own
+ *                          before the search, so that only an entry standing below the root reads the tables inside the frame loop)
+ * n_nodes == 0 or n_edges == 0: the plain search (its launches, its workspace), bias_sum / bias_node zero-filled.  The library checks
+ * the table SIZES only (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES) and that weight is finite; the contents are the caller's
+ * responsibility, as for avsr_beam_set_bias. */
+int64_t avsr_ctc_beam_bias_workspace_bytes(int B, int T, int W, int K);
+int avsr_ctc_beam_search_bias(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
+                              const int32_t* first, const int32_t* tok, const int32_t* child, const int32_t* unc, int n_nodes, int n_edges,
+                              float weight, int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid,
+                              float* bias_sum, int32_t* bias_node, void* workspace, int B, int T, int V, avsr_stream_t stream);
 /* Exact CTC log-likelihood of N label sequences per utterance against ONE copy of its log-posteriors: lp f32 [B][T][ld]; labels
  * int64 [B][N][Lmax] padded with ignore_id (Lmax <= 255); loglik f32 [B][N] = log P_ctc(labels | lp[b, :in_lens[b]]); no labels:
  * the sum of lp[t][blank]; a sequence that does not fit the frames: -inf. */

@@ -253,7 +253,7 @@ class ModelModule(_Base):
                                             topk=int(getattr(args, "rescore_topk", None) or 16), **kw)
         kw = {}
         bias = self._bias_scorer()
-        if bias is not None:  # (parse_args refuses the flags together with --decode-mode rescore)
+        if bias is not None:  # (either decoder takes it; eval.py's parse_args still refuses the flags with --decode-mode rescore)
             kw = dict(bias_phrases=bias, bias_weight=float(args.bias_weight))
         if not lm_path or lm_weight == 0.0:
             return make(self.model, self.token_list, **kw)
@@ -274,8 +274,6 @@ class ModelModule(_Base):
         args = getattr(self, "args", None)
         weight = float(getattr(args, "bias_weight", 0.0) or 0.0)
         path = getattr(args, "bias_list", None)
-        if getattr(args, "decode_mode", "search") == "rescore":
-            return None
         if weight == 0.0:
             if path:
                 import warnings
@@ -367,20 +365,41 @@ def _resolve_lm(model, token_list, rnnlm, rnnlm_conf, lm_weight, what="search"):
     return lm
 
 
+def _resolve_bias(token_list, bias_phrases, bias_weight, what="search"):
+    """The `bias` slot of the decoders below: None, or a ContextBiasScorer over the token list's vocabulary."""
+    bias = None
+    if bias_phrases is not None and bias_weight != 0.0:
+        from auto_avsr_amd.bias import ContextBiasScorer
+
+        bias = bias_phrases if isinstance(bias_phrases, ContextBiasScorer) else ContextBiasScorer(bias_phrases, len(token_list))
+        if bias.n_vocab != len(token_list):
+            raise ValueError(f"the bias scorer's vocabulary ({bias.n_vocab}) is not the token list's ({len(token_list)})")
+    elif bias_weight != 0.0:
+        import warnings
+
+        warnings.warn(f"bias_weight={bias_weight} without a bias list (bias_phrases is None): the {what} runs without biasing")
+    return bias
+
+
 def get_two_pass_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight=0.1, lm_weight=0.0, beam_size=16,
-                         topk=16, nbest=None):
+                         topk=16, nbest=None, bias_phrases=None, bias_weight=0.0):
     """Not in the reference: the scorers and weights of get_beam_search_decoder behind auto_avsr_amd.two_pass.TwoPassDecoder -- a
     CTC prefix beam search on the device (beam_size entries, topk tokens per frame) whose nbest (default: all beam_size) are
-    rescored by one teacher-forced decoder (+ language model) pass under the same objective."""
+    rescored by one teacher-forced decoder (+ language model) pass under the same objective.  bias_phrases / bias_weight as in
+    get_beam_search_decoder: the phrases are boosted inside the first pass (a boosted token still has to be among the frame's topk
+    tokens) and the bias term enters the rescoring objective."""
     from auto_avsr_amd.two_pass import TwoPassDecoder
     from espnet.nets.scorers.length_bonus import LengthBonus
 
     lm = _resolve_lm(model, token_list, rnnlm, rnnlm_conf, lm_weight, what="rescoring")
+    bias = _resolve_bias(token_list, bias_phrases, bias_weight, what="rescoring")
     sos = eos = model.odim - 1
     scorers = model.scorers()
     scorers["lm"] = lm
+    scorers["bias"] = bias
     scorers["length_bonus"] = LengthBonus(len(token_list))
-    weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight if lm is not None else 0.0, "length_bonus": penalty}
+    weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight if lm is not None else 0.0,
+               "bias": bias_weight if bias is not None else 0.0, "length_bonus": penalty}
     return TwoPassDecoder(scorers, weights, sos=sos, eos=eos, token_list=token_list, beam_size=beam_size, topk=topk, nbest=nbest,
                           blank=model.blank, ignore_id=model.ignore_id)
 
@@ -414,17 +433,7 @@ def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, pena
         import warnings
 
         warnings.warn(f"lm_weight={lm_weight} without a language model (rnnlm is None): the search runs without fusion")
-    bias = None
-    if bias_phrases is not None and bias_weight != 0.0:
-        from auto_avsr_amd.bias import ContextBiasScorer
-
-        bias = bias_phrases if isinstance(bias_phrases, ContextBiasScorer) else ContextBiasScorer(bias_phrases, len(token_list))
-        if bias.n_vocab != len(token_list):
-            raise ValueError(f"the bias scorer's vocabulary ({bias.n_vocab}) is not the token list's ({len(token_list)})")
-    elif bias_weight != 0.0:
-        import warnings
-
-        warnings.warn(f"bias_weight={bias_weight} without a bias list (bias_phrases is None): the search runs without biasing")
+    bias = _resolve_bias(token_list, bias_phrases, bias_weight)
     sos = eos = model.odim - 1
     scorers = model.scorers()
     scorers["lm"] = lm

@@ -42,7 +42,10 @@ def main():
     ap.add_argument("--bias", action="store_true",
                     help="contextual-biasing rows instead of the default ones: a list of 1 000 random phrases of 2 - 5 tokens, weight 1.0 -- the "
                          "native step without and with the list, alternated in the same run, and the python-issued step with the list "
-                         "(precise mode; python tools/bench_decode.py --bias > profiles/context_bias_decode.json)")
+                         "(precise mode; python tools/bench_decode.py --bias > profiles/context_bias_decode.json).  With --two-pass: two-pass "
+                         "decoding without and with the same list, alternated -- first pass and whole decode "
+                         "(python tools/bench_decode.py --two-pass --bias > profiles/two_pass_bias_decode.json)")
+    ap.add_argument("--bias-weight", type=float, default=1.0, help="--two-pass --bias: the weight of the list")
     ap.add_argument("--rescore-beam", type=int, default=16)
     ap.add_argument("--rescore-topk", type=int, default=16)
     ap.add_argument("--modes", type=str, default="precise", help="--two-pass: comma-separated numerical modes (eval.py decodes in precise)")
@@ -53,6 +56,8 @@ def main():
         return main_two_pass_sweep(args)
     if args.batch:
         return main_batch(args)
+    if args.bias and args.two_pass:
+        return main_two_pass_bias(args)
     if args.bias:
         return main_bias(args)
     if args.two_pass or args.two_pass_once:
@@ -494,6 +499,95 @@ def main_bias(args):
                                 "1 000 random 2 - 5-token phrases (plus a few cut out of the unbiased winner), and the python-issued step with it; video "
                                 "E2E 250M decoder, search only (encoder output ready), wall clock between synchronisations, one warm-up then "
                                 "the sides alternated",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def main_two_pass_bias(args):
+    import random
+    import statistics
+
+    import lightning
+    from synth import synth_batch, synth_state_dict
+
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode.py --two-pass --bias needs an MI355X: there is nothing to time without one")
+    dev = torch.device("cuda:0")
+    V = 5049
+    m = E2E(V, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    toks = [str(i) for i in range(V)]
+    rng = random.Random(11)
+    phrases = [[rng.randint(1, V - 2) for _ in range(rng.randint(2, 5))] for _ in range(1000)]
+    w_bias = args.bias_weight
+    AF.set_mode("precise")
+    rows = []
+    for T in (100, 400):
+        x, _, _ = synth_batch("video", 1, T, 3, V, seed=T, lengths=[T])
+        with torch.no_grad():
+            enc = m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float()
+        plain = lightning.get_two_pass_decoder(m, toks, beam_size=args.rescore_beam, topk=args.rescore_topk)
+        with torch.no_grad():
+            first = plain(enc)[0].asdict()["yseq"][1:-1]
+        # random phrases never meet a hypothesis: a few cut out of the unbiased winner make the list matter (the rest is its bulk)
+        hot = [first[i: i + 3] for i in range(0, max(1, len(first) - 3), 7)]
+        hot = [p for p in hot if p and all(1 <= t <= V - 2 for t in p)]
+        sides = {"no_list": plain, "with_list": lightning.get_two_pass_decoder(m, toks, beam_size=args.rescore_beam, topk=args.rescore_topk,
+                                                                               bias_phrases=phrases + hot, bias_weight=w_bias)}
+        with torch.no_grad():
+            _, hlens, lp = plain._posteriors([enc])
+        times, out, rows_of, failed = {k: {"first_pass": [], "whole_decode": []} for k in sides}, {}, {}, {}
+        for rep_ in range(args.reps + 1):  # first repetition = warm-up; the sides alternate within a repetition
+            for k, tp in sides.items():
+                for what, fn in (("first_pass", lambda: tp.first_pass(lp, hlens)), ("whole_decode", lambda: tp(enc))):
+                    if (k, what) in failed:
+                        continue
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    try:
+                        with torch.no_grad():
+                            res = fn()
+                    except RuntimeError as e:  # (the rescoring pass takes label rows of at most 255 tokens)
+                        failed[(k, what)] = str(e)
+                        continue
+                    torch.cuda.synchronize()
+                    if rep_:
+                        times[k][what].append((time.perf_counter() - t0) * 1e3)
+                    if what == "first_pass":
+                        rows_of[k] = int(res[0].shape[2])
+                    else:
+                        out[k] = res
+        sc = sides["with_list"].bias
+        row = {"T_frames": T, "beam": args.rescore_beam, "topk": args.rescore_topk, "mode": "precise", "vocabulary": V, "bias_weight": w_bias,
+               "phrases": len(sc.phrases), "trie_nodes": sc.n_nodes, "trie_edges": sc.n_edges, "root_fan_out": int(sc.first[1]),
+               "repetitions": args.reps, "sides": {}}
+        for k in sides:
+            row["sides"][k] = {what + "_ms": None if (k, what) in failed else
+                               {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+                               for what, ts in times[k].items()}
+            row["sides"][k]["longest_label_row"] = rows_of[k]
+            row["sides"][k]["best_bias_sum"] = out[k][0].asdict()["scores"].get("bias") if k in out else None
+            for what in ("first_pass", "whole_decode"):
+                if (k, what) in failed:
+                    row["sides"][k][what + "_error"] = failed[(k, what)]
+        for what in ("first_pass", "whole_decode"):
+            if any((k, what) in failed for k in sides):
+                continue
+            a, b = (row["sides"][k][what + "_ms"]["median"] for k in ("no_list", "with_list"))
+            row[f"list_cost_{what}_ms"] = round(b - a, 3)
+            row[f"list_cost_{what}_relative"] = round(b / a - 1.0, 4)
+        if len(out) == 2:
+            row["list_changes_best"] = out["with_list"][0].asdict()["yseq"] != out["no_list"][0].asdict()["yseq"]
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    AF.set_mode("bf16")
+    print(json.dumps({"metric": "contextual biasing in two-pass decoding: CTC prefix beam search on the device (first pass) and the whole decode "
+                                "(posteriors + first pass + teacher-forced rescoring) without and with a list of 1 000 random 2 - 5-token "
+                                "phrases (plus a few cut out of the unbiased winner); video E2E 250M, one utterance per launch, encoder output "
+                                "ready, wall clock between synchronisations, one warm-up then the sides alternated",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
 
 
