@@ -33,6 +33,9 @@ extern "C" int avsr_gemm(int layout, const void* A, int a_dtype, int lda, const 
     AVSR_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "gemm: operands must be 16-byte aligned");
     AVSR_REQUIRE(!(accumulate && c_dtype != 0), "gemm: accumulate needs an f32 output");
     AVSR_REQUIRE(!(split_k > 1 && !accumulate), "gemm: split-K needs accumulate=1");
+    // (partial sums cannot pass through an activation, a gate or a dropout mask, and the accumulate branch of epilogue_lds adds no residual)
+    AVSR_REQUIRE(!(accumulate && (act != 0 || gate != nullptr || drop_p > 0.f || resid != nullptr)),
+                 "gemm: accumulate takes bias and alpha only (no act, gate, dropout or resid)");
     AVSR_REQUIRE(!(precise && (a_dtype != 0 || b_dtype != 0)), "gemm: precise mode needs f32 operands");
     if (M <= 0 || N <= 0) return 0;
     AVSR_REQUIRE(K > 0, "gemm: K must be positive");

@@ -32,7 +32,10 @@ struct Params {
     int lda, ldb;
     int M, N, K;
     int k_chunk;  // K range handled per blockIdx.z (split-K); == K when not split
-    // epilogue, applied in this order:
+    // epilogue, applied in this order -- by a non-accumulating output.  An accumulating one (accumulate = 1: split-K partial sums,
+    // "+=") takes +bias (lead split) and *alpha ONLY: act, gate, dropout, resid, C2 and the column sums are not applied there.  The
+    // public entry points (avsr_gemm, avsr_gemm_bf16_nt / _h16_nt, avsr_gemm_f32s_nt) refuse the combination; internal callers (TN /
+    // convolution weight gradients, attention_kv.hip) set accumulate with `gate` carrying the zero page and rely on that branch.
     const float* bias;  // [N] or null
     int act;            // 0 none, 1 relu, 2 silu
     const void* gate;   // saved activation [M,ldg]: v = gate>0 ? v*gate_scale : 0 (ReLU/dropout backward)

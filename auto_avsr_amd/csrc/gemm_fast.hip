@@ -155,6 +155,10 @@ static int gemm16_nt_impl(int f16, const void* A, int lda, const void* B, const 
                           const void* resid, int resid_dtype, int ldr, void* C, int c_dtype, int ldc, int accumulate,
                           int split_k, int tile, float* colsum, void* c2, int ldc2, hipStream_t stream) {
     AVSR_REQUIRE(!(colsum && accumulate), "gemm_bf16_nt: colsum needs a non-accumulating output");
+    // (partial sums cannot pass through an activation, a gate or a dropout mask, and the accumulate branch of epilogue_lds adds no residual)
+    AVSR_REQUIRE(!(accumulate && (act != 0 || gate != nullptr || drop_p > 0.f || resid != nullptr || c2 != nullptr)),
+                 f16 ? "gemm_h16_nt: accumulate takes bias and alpha only (no act, gate, dropout, resid or twin)"
+                     : "gemm_bf16_nt: accumulate takes bias and alpha only (no act, gate, dropout, resid or twin)");
     AVSR_REQUIRE(K > 0 && K % 64 == 0, "gemm_bf16_nt: K must be a positive multiple of 64");
     AVSR_REQUIRE(lda % 8 == 0 && ldb % 8 == 0, "gemm_bf16_nt: lda/ldb must be multiples of 8 elements");
     AVSR_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "gemm_bf16_nt: operands must be 16-byte aligned");

@@ -372,6 +372,9 @@ extern "C" int avsr_gemm_f32s_nt(const float* A, int lda, const float* B, int ld
                                  const void* resid, int resid_dtype, int ldr, void* C, int c_dtype, int ldc, int accumulate,
                                  int split_k, int tile, float* colsum, int b_split, void* c2, int ldc2, hipStream_t stream) {
     AVSR_REQUIRE(!(colsum && accumulate), "gemm_f32s_nt: colsum needs a non-accumulating output");
+    // (partial sums cannot pass through an activation, a gate or a dropout mask, and the accumulate branch of epilogue_lds adds no residual)
+    AVSR_REQUIRE(!(accumulate && (act != 0 || gate != nullptr || drop_p > 0.f || resid != nullptr || c2 != nullptr)),
+                 "gemm_f32s_nt: accumulate takes bias and alpha only (no act, gate, dropout, resid or twin)");
     AVSR_REQUIRE(!(c2 && (accumulate || c_dtype != 0)), "gemm_f32s_nt: the bf16 twin needs a non-accumulating f32 output");
     AVSR_REQUIRE(K > 0 && K % 64 == 0, "gemm_f32s_nt: K must be a positive multiple of 64");
     AVSR_REQUIRE(lda % 4 == 0 && ldb % 4 == 0, "gemm_f32s_nt: lda/ldb must be multiples of 4 elements");

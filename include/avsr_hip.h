@@ -57,6 +57,8 @@ int avsr_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float
  *   -> dropout(drop_p, seed) -> *alpha -> +resid[m,n] -> store (c_dtype) or atomicAdd (accumulate=1, f32).
  * seed_dev / alpha_dev (may be NULL): device-resident scalars added to seed / multiplied into alpha, so that a
  * captured hipGraph replays with fresh dropout masks and live upstream gradients.
+ * accumulate=1 applies +bias and *alpha ONLY (partial sums cannot pass through an activation, gate or dropout mask; no resid is
+ * added): combined with act != 0, gate, drop_p > 0 or resid the call is refused.
  * split_k>1 requires accumulate=1.  force_tile: 0 auto, 64 or 128. */
 int avsr_gemm(int layout, const void* A, int a_dtype, int lda, const void* B, int b_dtype, int ldb,
               int M, int N, int K, int precise, const float* bias, int act, const void* gate,
@@ -374,7 +376,8 @@ int avsr_avgpool_bwd(const float* dy, void* dx, int dtype, int64_t groups, int w
 
 /* ---- tuned bf16 NT GEMM (gemm_fast.hip): LDS-DMA operand ring, swizzled LDS, counted vmcnt ------------------ */
 /* C[M,N] = epi(A[M,K] . B[N,K]^T), A and B bf16 k-contiguous, K % 64 == 0; epilogue as avsr_gemm (resid may be
- * f32 or bf16); tile: 0 auto, 1 = 64x64, 2 = 128x64, 3 = 128x128 (3-stage ring, 4 waves), 4 = 128x128 with a 2-stage
+ * f32 or bf16; accumulate = 1 takes bias and alpha only and is refused with act, gate, dropout or resid, as in avsr_gemm);
+ * tile: 0 auto, 1 = 64x64, 2 = 128x64, 3 = 128x128 (3-stage ring, 4 waves), 4 = 128x128 with a 2-stage
  * ring, 5 = 256x128 with 8 waves, 6 = 256x128 with 4 waves, 7 = 128x64 with a 2-stage ring, 8 = 256x64 with 8 waves */
 int avsr_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const float* bias, int act,
                       const void* gate, int gate_dtype, int ldg, float gate_scale, float drop_p, uint64_t seed,
@@ -385,7 +388,8 @@ int avsr_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, int M, int
 /* ---- tuned NT GEMM of the precise mode (gemm_split.hip): f32 operands, split hi + lo bf16 planes formed in registers --------- */
 /* C[M,N] = epi(A[M,K] . B[N,K]^T), A and B f32 k-contiguous (lda, ldb % 4 == 0), K % 64 == 0; three bf16 MFMAs per product
  * (the arithmetic of avsr_gemm with precise = 1) on the LDS-DMA operand ring of avsr_gemm_bf16_nt; epilogue and arguments as
- * avsr_gemm_bf16_nt; tile: 0 auto, 1 = 64x64 / 3 stages, 2 = 64x64 / 2 stages, 3 = 128x64 / 2 stages, 4 = 128x128 / 2 stages,
+ * avsr_gemm_bf16_nt (accumulate = 1: bias and alpha only, refused with act, gate, dropout, resid or c2);
+ * tile: 0 auto, 1 = 64x64 / 3 stages, 2 = 64x64 / 2 stages, 3 = 128x64 / 2 stages, 4 = 128x128 / 2 stages,
  * 5 / 6 = 3 / 4 with 3 stages, 7 = 128x64 / 2 stages with a 4 x 1 wave grid, 11 .. 16 = 1 .. 6 with the staged A tile converted to
  * split8 in place once per stage (the default) instead of on every fragment read.
  * Forward contractions of the precise / hpf modes: positionwise_feed_forward.py:24-30, attention.py:31-34,123,
