@@ -121,7 +121,7 @@ class NativeBeam:
         # weight caches is part of the key, so the stacked copies below are rebuilt after native training steps too)
         from . import functional as AF
 
-        key = (str(dev), pe.data_ptr(), pe.shape[0], AF._wgen["gen"]) + tuple((p.data_ptr(), p._version) for p in params)
+        key = (str(dev), pe.data_ptr(), pe.shape[0], AF.weight_generation()) + tuple((p.data_ptr(), p._version) for p in params)
         if lm is not None:
             key += (lm_pe.data_ptr(), lm_pe.shape[0], float(bs.weights["lm"]))
         if key == self.key:

@@ -21,6 +21,8 @@ re-exported here (bottom of the file), so callers keep saying ``functional.<name
 import contextlib
 import os
 import math
+import struct
+import weakref
 
 import torch
 
@@ -366,11 +368,7 @@ def _rows(x):
     return x.numel() // x.shape[-1]
 
 
-# ---- bf16 weight copies for the tuned NT kernel ---------------------------------------------------------------
-# In bench (bf16) mode every contraction runs as C = A . B^T with both operands bf16 and k-contiguous
-# (csrc/gemm_fast.hip).  Weights therefore need a bf16 copy ([out][in], Linear forward) and a transposed bf16 copy
-# ([in][out_padded_to_64], data gradient).  Copies are cached per parameter version: an optimizer step bumps
-# `_version`, so they are rebuilt exactly once per training step (bench.py invalidates explicitly).
+# ---- A/B switches of the sub-layer families (read through this module) ------------------------------------------------------
 _BN_SMALL = os.environ.get("AVSR_BN_SMALL", "1") != "0"  # A/B switch: single-launch BatchNorm1d of the convolution module
 # A/B switch (round 6): GLU -> depthwise conv -> BatchNorm -> SiLU of the convolution module as one launch each way
 # (csrc/convmod_fused.hip).  OFF by default -- measured SLOWER than the launches it merges: a block must own every frame of its 8
@@ -391,13 +389,114 @@ _FUSE_QKV = os.environ.get("AVSR_FUSE_QKV", "1") != "0"  # A/B switch for the fu
 # reduce pass runs on the pooled tensors, the apply pass gathers the pooled gradient).  Measured on MI355X (round 2):
 # 22.98 -> 22.39 ms per step together with the hardware-reciprocal sigmoid.  AVSR_FUSE_STEM_POOL=0 restores the three-pass path.
 _FUSE_STEM_POOL = os.environ.get("AVSR_FUSE_STEM_POOL", "1") != "0"
-_wcache = {}   # (data_ptr, transposed, shape) -> [version, bf16 copy, source weight, is a slice of a concatenation]
+
+
+# ---- derived weight copies ------------------------------------------------------------------------------------------
+# Six kinds of copy are kept per parameter version, each at a stable address (captured graphs replay against them): bf16
+# Linear / conv copies (this section's end), split8 Linear / conv copies and two-plane f16 Linear / conv copies (below).  All
+# entries of one kind are rewritten by ONE launch of a table kernel; the tables are records of three C structs
+# (include/avsr_hip.h: avsr_multi_cast_transpose, avsr_multi_weight_permute, avsr_multi_split_pack).
+class _Copies:
+    """The entries of one kind of copy, key -> [version, copy, weight, ...], and the device table that rewrites them in one launch.
+    record((key, entry), blk0) -> (packed table record, its blocks, its taps); launch(table, n, blocks, max_taps);
+    rows (optional): the (key, entry) pairs to refresh -> what `record` is called with, when that is not one record per entry."""
+
+    def __init__(self, record, launch, rows=None):
+        self.entries, self.record, self.launch, self.rows = {}, record, launch, rows or (lambda todo: todo)
+        self.sig = self.table = None
+
+    def clear(self):
+        self.entries.clear()
+        self.sig = self.table = None
+
+    def refresh(self, todo=None, sig=None):
+        """Rewrite the copies of `todo` ((key, entry) pairs; default: all) and stamp them current.  The table is rebuilt -- a
+        host-to-device copy: never inside a capture -- only when `sig` (default: the number of entries) is not the one it was
+        built for (`self.sig = None` forces it: entries replaced, another `todo` of the same size)."""
+        if todo is None:
+            todo = self.entries.items()
+        if not todo:
+            return
+        if sig is None:
+            sig = len(self.entries)
+        if self.sig != sig:
+            recs, blocks, max_taps = [], 0, 1
+            for row in self.rows(todo):
+                rec, blk, taps = self.record(row, blocks)
+                recs.append(rec)
+                blocks += blk
+                max_taps = max(max_taps, taps)
+            host = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
+            self.table = (host.to(next(iter(todo))[1][2].device), len(recs), blocks, max_taps)
+            self.sig = sig
+        self.launch(*self.table)
+        for _, ent in todo:
+            ent[0] = ent[2]._version
+
+
+def _cast_record(src, dst, dstT, R, C, ldT, limT, code, blk0):
+    """avsr_multi_cast_transpose: src [R][C] f32 -> dst [R][C] and / or dstT [C][ldT] (zero tail up to limT); code 0 bf16, 2 =
+    the two-plane f16 image [R][2][C] in dst."""
+    tiles_c = (C + 63) // 64
+    return (struct.pack("<QQQiiiiiiii", src.data_ptr(), dst.data_ptr() if dst is not None else 0,
+                        dstT.data_ptr() if dstT is not None else 0, R, C, ldT, blk0, tiles_c, limT, code, 0),
+            (max(R, limT) + 63) // 64 * tiles_c, 1)
+
+
+def _permute_record(code):
+    """avsr_multi_weight_permute: conv weight -> [Cout][taps][Cin] ([Cin][taps][Cout] when the key says to_dgrad); code 0 bf16,
+    3 split8, 2 = the two-plane f16 image."""
+    def record(item, blk0):
+        key, ent = item
+        to_dgrad = len(key) == 3 and key[1]   # bf16 keys are (data_ptr, to_dgrad, shape); the other kinds keep the forward layout only
+        Cout, Cin, taps = ent[2].shape[0], ent[2].shape[1], ent[2][0, 0].numel()
+        return (struct.pack("<QQiiiiiiii", ent[2].data_ptr(), ent[1].data_ptr(), Cout, Cin, taps, int(to_dgrad), blk0, code, 0, 0),
+                ops.weight_permute_blocks(Cout, Cin, to_dgrad), taps)
+    return record
+
+
+def _split_record(item, blk0):
+    """avsr_multi_split_pack"""
+    ent = item[1]
+    n = ent[2].numel()
+    return struct.pack("<QQqq", ent[2].data_ptr(), ent[1].data_ptr(), n // 8, blk0), (n + 2047) // 2048, 1
+
+
+def _h16_record(item, blk0):
+    ent = item[1]
+    R, C = ent[2].shape
+    return _cast_record(ent[2], ent[1], None, R, C, 0, 0, 2, blk0)
+
+
+def _bf16_record(group, blk0):
+    """one record per WEIGHT, carrying both of its bf16 copies (a row of weight_cast_groups())"""
+    w, dst, dstT, R, C, ldT, limT = group
+    return _cast_record(w, dst, dstT, R, C, ldT, limT, 0, blk0)
+
+
+# (the launchers look the binding up at call time: tests and profilers replace ops.multi_*)
+def _launch_cast(table, n, blocks, max_taps):
+    ops.multi_cast_transpose(table, n, blocks)
+
+
+def _launch_permute(table, n, blocks, max_taps):
+    ops.multi_weight_permute(table, n, blocks, max_taps)
+
+
+def _launch_split(table, n, blocks, max_taps):
+    ops.multi_split_pack(table, n, blocks)
+
+
+# ---- bf16 weight copies for the tuned NT kernel ---------------------------------------------------------------
+# In bench (bf16) mode every contraction runs as C = A . B^T with both operands bf16 and k-contiguous
+# (csrc/gemm_fast.hip).  Weights therefore need a bf16 copy ([out][in], Linear forward) and a transposed bf16 copy
+# ([in][out_padded_to_64], data gradient).  Copies are cached per parameter version: an optimizer step bumps
+# `_version`, so they are rebuilt exactly once per training step (bench.py invalidates explicitly).
+_bf16_copies = _Copies(_bf16_record, _launch_cast, rows=lambda todo: weight_cast_groups()[1])
+_wcache = _bf16_copies.entries  # (data_ptr, transposed, shape) -> [version, bf16 copy, source weight, is a slice of a concatenation]
 _wcat = {}     # (data_ptrs..., transposed) -> concatenated bf16 buffer whose slices are registered in _wcache
-_wtable = {"n": 0, "dev": None, "blocks": 0, "built_for": -1}
-
-
-_wconv = {}    # (data_ptr, to_dgrad, shape) -> [version, bf16 permuted copy, conv weight]
-_wconv_table = {"n": 0, "dev": None, "blocks": 0, "built_for": -1}
+_conv_copies = _Copies(_permute_record(0), _launch_permute)
+_wconv = _conv_copies.entries   # (data_ptr, to_dgrad, shape) -> [version, bf16 permuted copy, conv weight]
 
 
 # "gen": bumped whenever weights change behind the tensor version counter (note_optimizer_step); the side caches that only
@@ -407,55 +506,19 @@ _wgen = {"cleared": 0, "owner": None, "owner_gen": None, "dirty": 0, "gen": 0, "
 
 # ---- pre-split weights of the precise / hpf forward pass (csrc/gemm_split.hip, split8 layout) ---------------------------------
 # The B operand of every forward contraction is a parameter: its hi / lo bf16 planes are formed once per step (ONE multi-tensor
-# launch for all Linear-type weights, one small launch per conv weight for the permuted copies) instead of on every fragment
+# launch for all Linear-type weights, one for the permuted copies of all conv weights) instead of on every fragment
 # of every tile that reads it.  Cached per parameter version like the bf16 copies; addresses stay stable for captured graphs.
 _SPLIT_W = os.environ.get("AVSR_SPLIT_WEIGHTS", "1") != "0"
-_wsplit = {}    # (data_ptr, shape) -> [version, Split8 copy, weight]
-_wsplit_conv = {}  # (data_ptr, shape) -> [version, Split8 permuted copy, conv weight]
-_wsplit_table = {"n": 0, "dev": None, "blocks": 0, "built_for": -1}
-
-
-_wsplit_conv_table = {"n": 0, "dev": None, "blocks": 0, "built_for": -1, "max_taps": 1}
+_split_copies = _Copies(_split_record, _launch_split)
+_wsplit = _split_copies.entries    # (data_ptr, shape) -> [version, Split8 copy, weight]
+_split_conv_copies = _Copies(_permute_record(3), _launch_permute)
+_wsplit_conv = _split_conv_copies.entries  # (data_ptr, shape) -> [version, Split8 permuted copy, conv weight]
 
 
 def _refresh_split_weights():
     _wgen["split_gen"] = _wgen["gen"]
-    if _wsplit_conv:
-        # round 6: every permuted split8 conv copy in ONE launch of the table kernel (csrc/gemm_conv.hip, entry code 3) -- until
-        # round 5 one 5 us launch per convolution weight at the start of every step
-        if _wsplit_conv_table["built_for"] != len(_wsplit_conv):
-            import struct
-
-            blob, blk, max_taps = b"", 0, 1
-            for (ptr, shape), ent in _wsplit_conv.items():
-                Cout, Cin = shape[0], shape[1]
-                taps = ent[2][0, 0].numel()
-                blob += struct.pack("<QQiiiiiiii", ent[2].data_ptr(), ent[1].data_ptr(), Cout, Cin, taps, 0, blk, 3, 0, 0)
-                blk += ops.weight_permute_blocks(Cout, Cin, False)
-                max_taps = max(max_taps, taps)
-            dev = next(iter(_wsplit_conv.values()))[2].device
-            host = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-            _wsplit_conv_table.update(n=len(_wsplit_conv), dev=host.to(dev), blocks=blk, built_for=len(_wsplit_conv), max_taps=max_taps)
-        ops.multi_weight_permute(_wsplit_conv_table["dev"], _wsplit_conv_table["n"], _wsplit_conv_table["blocks"],
-                                 _wsplit_conv_table["max_taps"])
-        for ent in _wsplit_conv.values():
-            ent[0] = ent[2]._version
-    if not _wsplit:
-        return
-    if _wsplit_table["built_for"] != len(_wsplit):
-        import struct
-
-        blob, blk = b"", 0
-        for ent in _wsplit.values():
-            n = ent[2].numel()
-            blob += struct.pack("<QQqq", ent[2].data_ptr(), ent[1].data_ptr(), n // 8, blk)
-            blk += (n + 2047) // 2048
-        dev = next(iter(_wsplit.values()))[2].device
-        host = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-        _wsplit_table.update(n=len(_wsplit), dev=host.to(dev), blocks=blk, built_for=len(_wsplit))
-    ops.multi_split_pack(_wsplit_table["dev"], _wsplit_table["n"], _wsplit_table["blocks"])
-    for ent in _wsplit.values():
-        ent[0] = ent[2]._version
+    _split_conv_copies.refresh()
+    _split_copies.refresh()
 
 
 def _w_split(w2d):
@@ -472,7 +535,6 @@ def _w_split(w2d):
         return ent[1]
     if ent is None:
         ent = _wsplit[key] = [-1, ops.split_pack(w2d), w2d]
-        _wsplit_table["built_for"] = -1
     else:
         ops.split_pack(w2d, out=ent[1])
     ent[0] = w2d._version
@@ -504,11 +566,9 @@ def _w_conv_split(w):
 # refreshed by ONE multi-tensor launch per step (avsr_multi_cast_transpose, dst dtype 2) or by the optimizer's own tile pass;
 # several weights may be rows of one concatenated buffer (the fused Q/K/V and all-layer position projections).  A component on
 # "f16" reads the hi rows only (pitch 2 K); "f16x2" reads both planes (two MFMAs per product, exact weights): _h16_nt().
-_wh16 = {}       # (data_ptr, shape) -> [version, two-plane f16 copy (possibly a row slice of a concatenation), weight]
+_h16_copies = _Copies(_h16_record, _launch_cast)
+_wh16 = _h16_copies.entries  # (data_ptr, shape) -> [version, two-plane f16 copy (possibly a row slice of a concatenation), weight]
 _wh16_cat = {}   # (data_ptrs...) -> concatenated f16 buffer
-_wh16_table = {"n": 0, "dev": None, "blocks": 0, "built_for": -1}
-
-
 _wh16_owned = set()  # keys of _wh16 whose copy an optimizer rewrites inside its own update pass (optim.FusedAdamW cast_weights)
 
 
@@ -523,51 +583,17 @@ def claim_h16_copies(keys):
     keys = set(keys)
     if keys != _wh16_owned:
         _wh16_owned = keys
-        _wh16_table["built_for"] = -1
+        _h16_copies.sig = None
 
 
 def _refresh_h16_weights(everything=False):
     """everything: also the copies an optimizer owns (a weight changed behind its back, or a copy that was just registered)."""
     _wgen["h16_gen"] = _wgen["gen"]
-    _refresh_h16_conv_weights()
-    if not _wh16:
-        return
+    _conv_h16_copies.refresh()
     owner = _wgen["owner"]() if _wgen["owner"] is not None else None
     owned = _wh16_owned if (not everything and owner is not None and _wgen["owner_gen"] == _cast_generation()) else set()
     todo = [(k, ent) for k, ent in _wh16.items() if k not in owned]
-    if not todo:
-        return
-    if _wh16_table["built_for"] != (len(_wh16), len(todo)):
-        import struct
-
-        blob, blk = b"", 0
-        for (ptr, shape), ent in todo:
-            R, C = shape
-            tiles_c, tiles_r = (C + 63) // 64, (R + 63) // 64
-            blob += struct.pack("<QQQiiiiiiii", ent[2].data_ptr(), ent[1].data_ptr(), 0, R, C, 0, blk, tiles_c, 0, 2, 0)
-            blk += tiles_r * tiles_c
-        dev = todo[0][1][2].device
-        host = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-        _wh16_table.update(n=len(todo), dev=host.to(dev), blocks=blk, built_for=(len(_wh16), len(todo)))
-    ops.multi_cast_transpose(_wh16_table["dev"], _wh16_table["n"], _wh16_table["blocks"])
-    for _, ent in todo:
-        ent[0] = ent[2]._version
-
-
-def _cast_h16_entries(ents):
-    """(Re)write the two-plane copies of the given cache entries with one multi-tensor launch over a table built on the spot."""
-    import struct
-
-    blob, blk = b"", 0
-    for ent in ents:
-        R, C = ent[2].shape
-        tiles_c, tiles_r = (C + 63) // 64, (R + 63) // 64
-        blob += struct.pack("<QQQiiiiiiii", ent[2].data_ptr(), ent[1].data_ptr(), 0, R, C, 0, blk, tiles_c, 0, 2, 0)
-        blk += tiles_r * tiles_c
-    table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(ents[0][2].device)
-    ops.multi_cast_transpose(table, len(ents), blk)
-    for ent in ents:
-        ent[0] = ent[2]._version
+    _h16_copies.refresh(todo, sig=(len(_wh16), len(todo)))
 
 
 def _w_h16(w2d):
@@ -583,8 +609,8 @@ def _w_h16(w2d):
     assert w2d.dtype == torch.float32 and w2d.is_contiguous()
     if ent is None:
         ent = _wh16[key] = [-1, torch.empty(w2d.shape[0], 2, w2d.shape[1], dtype=torch.float16, device=w2d.device), w2d]
-        _wh16_table["built_for"] = -1
-    _cast_h16_entries([ent])  # (this copy alone: a one-entry table -- registration happens once per weight, outside any capture)
+    # this copy alone: a one-entry table built on the spot -- registration happens once per weight, outside any capture
+    _Copies(_h16_record, _launch_cast).refresh([(key, ent)])
     return ent[1]
 
 
@@ -602,7 +628,7 @@ def _w_h16_cat(ws):
             _wh16[(w.data_ptr(), tuple(w.shape))] = [-1, buf[off:off + w.shape[0]], w]
             off += w.shape[0]
         _wh16_cat[key] = buf
-        _wh16_table["built_for"] = -1
+        _h16_copies.sig = None
     for w in ws:
         _w_h16(w)  # (re-casts a slice whose weight changed version; everything after an optimizer step)
     return buf
@@ -618,29 +644,8 @@ def _h16_nt(a, lda, wbuf, M, N, K, out, ldc, planes=None, **kw):
     return ops.gemm_h16_nt(a, lda, wbuf[:, 0], 2 * K, M, N, K, out, ldc, B_lo=wbuf[:, 1] if planes == 2 else None, **kw)
 
 
-_wconv16 = {}   # (data_ptr, shape) -> [version, two-plane f16 [Cout][2][taps * Cin] copy, conv weight]
-_wconv16_table = {"n": 0, "dev": None, "blocks": 0, "built_for": -1, "max_taps": 1}
-
-
-def _refresh_h16_conv_weights():
-    if not _wconv16:
-        return
-    if _wconv16_table["built_for"] != len(_wconv16):
-        import struct
-
-        blob, blk, max_taps = b"", 0, 1
-        for (ptr, shape), ent in _wconv16.items():
-            Cout, Cin = shape[0], shape[1]
-            taps = ent[2][0, 0].numel()
-            blob += struct.pack("<QQiiiiiiii", ent[2].data_ptr(), ent[1].data_ptr(), Cout, Cin, taps, 0, blk, 2, 0, 0)
-            blk += ops.weight_permute_blocks(Cout, Cin, False)
-            max_taps = max(max_taps, taps)
-        dev = next(iter(_wconv16.values()))[2].device
-        host = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-        _wconv16_table.update(n=len(_wconv16), dev=host.to(dev), blocks=blk, built_for=len(_wconv16), max_taps=max_taps)
-    ops.multi_weight_permute(_wconv16_table["dev"], _wconv16_table["n"], _wconv16_table["blocks"], _wconv16_table["max_taps"])
-    for ent in _wconv16.values():
-        ent[0] = ent[2]._version
+_conv_h16_copies = _Copies(_permute_record(2), _launch_permute)
+_wconv16 = _conv_h16_copies.entries   # (data_ptr, shape) -> [version, two-plane f16 [Cout][2][taps * Cin] copy, conv weight]
 
 
 def _w_conv_h16(w):
@@ -656,8 +661,7 @@ def _w_conv_h16(w):
         return ent[1]
     if ent is None:
         ent = _wconv16[key] = [-1, torch.empty(w.shape[0], 2, w[0].numel(), dtype=torch.float16, device=w.device), w]
-        _wconv16_table["built_for"] = -1
-    _refresh_h16_conv_weights()
+    _conv_h16_copies.refresh()
     return ent[1]
 
 
@@ -673,6 +677,12 @@ def note_optimizer_step(linear_copies_rewritten: bool):
     after native training) -- brings them up to date."""
     _wgen["dirty"] = max(_wgen["dirty"], 1 if linear_copies_rewritten else 2)
     _wgen["gen"] += 1
+
+
+def weight_generation():
+    """Counter of the optimizer steps that changed weights behind the tensor version counter (note_optimizer_step): part of the
+    key of anything derived from weights outside these caches."""
+    return _wgen["gen"]
 
 
 def _cast_generation():
@@ -699,52 +709,19 @@ def weight_cast_groups():
 def claim_weight_casts(owner, generation):
     """`owner` (held weakly) has just rewritten every copy listed by weight_cast_groups() at `generation` and will do so
     after each of its steps: refresh_weight_cache() skips the Linear re-cast while that stays true."""
-    import weakref
-
     _wgen["owner"] = weakref.ref(owner) if owner is not None else None
     _wgen["owner_gen"] = generation
 
 
 def invalidate_weight_cache():
-    _wcache.clear()
+    for copies in (_bf16_copies, _conv_copies, _split_copies, _split_conv_copies, _h16_copies, _conv_h16_copies):
+        copies.clear()
     _wcat.clear()
-    _wconv.clear()
-    _wsplit.clear()
-    _wsplit_conv.clear()
-    _wsplit_conv_table.update(n=0, dev=None, blocks=0, built_for=-1, max_taps=1)
-    _wsplit_table.update(n=0, dev=None, blocks=0, built_for=-1)
-    _wh16.clear()
     _wh16_cat.clear()
     _wh16_owned.clear()
-    _wh16_table.update(n=0, dev=None, blocks=0, built_for=-1)
-    _wconv16.clear()
-    _wconv16_table.update(n=0, dev=None, blocks=0, built_for=-1, max_taps=1)
     _wgen["cleared"] += 1
     _wgen["owner"] = None
     _wgen["dirty"] = 0
-    _wtable.update(n=0, dev=None, blocks=0, built_for=-1)
-    _wconv_table.update(n=0, dev=None, blocks=0, built_for=-1)
-
-
-def _refresh_conv_weights():
-    if not _wconv:
-        return
-    if _wconv_table["built_for"] != len(_wconv):
-        import struct
-
-        blob, blk, max_taps = b"", 0, 1
-        for (ptr, to_dgrad, shape), ent in _wconv.items():
-            Cout, Cin = shape[0], shape[1]
-            taps = ent[2][0, 0].numel()
-            blob += struct.pack("<QQiiiiiiii", ent[2].data_ptr(), ent[1].data_ptr(), Cout, Cin, taps, int(to_dgrad), blk, 0, 0, 0)
-            blk += ops.weight_permute_blocks(Cout, Cin, to_dgrad)
-            max_taps = max(max_taps, taps)
-        dev = next(iter(_wconv.values()))[2].device
-        host = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-        _wconv_table.update(n=len(_wconv), dev=host.to(dev), blocks=blk, built_for=len(_wconv), max_taps=max_taps)
-    ops.multi_weight_permute(_wconv_table["dev"], _wconv_table["n"], _wconv_table["blocks"], _wconv_table["max_taps"])
-    for ent in _wconv.values():
-        ent[0] = ent[2]._version
 
 
 def _w_conv(w, to_dgrad):
@@ -761,10 +738,7 @@ def _w_conv(w, to_dgrad):
     if ent is None:
         ent = _wconv[key] = [-1, ops.conv_weight_permute(w, torch.bfloat16, to_dgrad=to_dgrad), w]
     else:  # stale: refresh in place (addresses stay stable for captured graphs)
-        Cout, Cin = w.shape[0], w.shape[1]
-        taps = w[0, 0].numel()
-        ops.call("avsr_conv_weight_permute", w.data_ptr(), ent[1].data_ptr(), 1, Cout, Cin, taps, int(to_dgrad),
-                 taps * (Cout if to_dgrad else Cin), ops._stream(w))
+        ops.conv_weight_permute(w, torch.bfloat16, to_dgrad=to_dgrad, out=ent[1])
     ent[0] = w._version
     return ent[1]
 
@@ -788,33 +762,15 @@ def refresh_weight_cache(force=False):
     force: re-cast even when an optimizer has claimed the copies (a weight was changed behind its back, e.g. by
     load_state_dict -- detected through the tensor version in _w_bf16)."""
     dirty, _wgen["dirty"] = _wgen["dirty"], 0
-    _refresh_conv_weights()
+    _conv_copies.refresh()
     if (_state["precise"] or _state["hpf"]) and (_wsplit or _wsplit_conv):
         _refresh_split_weights()
     if _state["mixed"] and (_wh16 or _wconv16):
         _refresh_h16_weights()
-    if not _wcache:
-        return
     owner = _wgen["owner"]() if _wgen["owner"] is not None else None
     if not force and dirty < 2 and owner is not None and _wgen["owner_gen"] == _cast_generation():
         return  # the optimizer step rewrote every copy together with the weights (optim.FusedAdamW cast_weights=True)
-    if _wtable["built_for"] != len(_wcache):
-        import struct
-
-        blob, blk = b"", 0
-        groups = weight_cast_groups()[1]
-        for (w, dst, dstT, R, C, ldT, limT) in groups:
-            tiles_c = (C + 63) // 64
-            tiles_r = (max(R, limT) + 63) // 64
-            blob += struct.pack("<QQQiiiiiiii", w.data_ptr(), dst.data_ptr() if dst is not None else 0,
-                                dstT.data_ptr() if dstT is not None else 0, R, C, ldT, blk, tiles_c, limT, 0, 0)
-            blk += tiles_r * tiles_c
-        dev = groups[0][0].device
-        host = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-        _wtable.update(n=len(groups), dev=host.to(dev), blocks=blk, built_for=len(_wcache))
-    ops.multi_cast_transpose(_wtable["dev"], _wtable["n"], _wtable["blocks"])
-    for ent in _wcache.values():
-        ent[0] = ent[2]._version
+    _bf16_copies.refresh()
 
 
 def _w_bf16(w2d, transposed):
@@ -860,7 +816,7 @@ def _w_bf16_cat(ws, transposed):
             _wcache[(w.data_ptr(), transposed, tuple(w.shape))] = [-1, sl, w, True]
             off += w.shape[0]
         _wcat[key] = buf
-        _wtable["built_for"] = -1
+        _bf16_copies.sig = None
         refresh_weight_cache()
     else:
         for w in ws:

@@ -93,7 +93,7 @@ class TransformerLM(BatchScorerInterface, nn.Module):
         """Tensors computed from the parameters, rebuilt when a parameter changes: the input table [V][D] = embed followed by
         encoder.embed.0 (a token's input row is a gather, not a contraction) and the stacked Q / K / V projections per layer."""
         params = list(self.parameters())
-        key = (AF._wgen["gen"],) + tuple((p.data_ptr(), p._version) for p in params)
+        key = (AF.weight_generation(),) + tuple((p.data_ptr(), p._version) for p in params)
         if self._derived is None or self._derived[0] != key:
             lin = self.encoder.embed[0]
             with torch.no_grad(), AF.precise():

@@ -723,14 +723,17 @@ def log_softmax(x, ld, rows, V):
 
 
 # ---------------------------------------------------------------------------------------------- convolutions
-def conv_weight_permute(w, out_dtype, to_dgrad=False, ld_out=None):
-    """torch conv weight [Cout, Cin, *taps] (f32) -> [Cout][taps][Cin] (or [Cin][taps][Cout] for the data gradient)."""
+def conv_weight_permute(w, out_dtype, to_dgrad=False, ld_out=None, out=None):
+    """torch conv weight [Cout, Cin, *taps] (f32) -> [Cout][taps][Cin] (or [Cin][taps][Cout] for the data gradient);
+    out: an earlier result of the same arguments, rewritten in place."""
     Cout, Cin = w.shape[0], w.shape[1]
     taps = w[0, 0].numel()
     a, b = (Cin, Cout) if to_dgrad else (Cout, Cin)
     ld = ld_out or taps * b
-    alloc = torch.zeros if ld != taps * b else torch.empty
-    out = alloc(a, ld, dtype=out_dtype, device=w.device)
+    if out is None:
+        alloc = torch.zeros if ld != taps * b else torch.empty
+        out = alloc(a, ld, dtype=out_dtype, device=w.device)
+    assert out.shape == (a, ld) and out.dtype == out_dtype
     # (this entry point's dtype code 2 is the split8 layout; IEEE half is 3)
     call("avsr_conv_weight_permute", _ptr(w), _ptr(out), 3 if out_dtype == torch.float16 else dt(out), Cout, Cin, taps,
          int(to_dgrad), ld, _stream(w))
