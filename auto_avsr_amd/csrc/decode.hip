@@ -48,13 +48,8 @@ namespace {
 constexpr float LOGZERO = -10000000000.0f;
 constexpr int MAX_BEAM = 128;
 
-struct IdxList {
-    int n;
-    int idx[MAX_BEAM];
-};
-
-// A GROUP of utterances decoded together (avsr_beam_*_batch): the running hypotheses of all of them are one packed row list, every
-// utterance at the same position L.  Utterance u owns rows [off, off + n) of the current beam and rows [noff, noff + nn) of the
+// A GROUP of utterances decoded together (avsr_beam_*_batch; a search of one utterance is a group of one): the running hypotheses
+// of all of them are one packed row list, every utterance at the same position L.  Utterance u owns rows [off, off + n) of the current beam and rows [noff, noff + nn) of the
 // beam a kernel writes; f0 = frames of the utterances before it (its memory K / V, CTC state and r_new regions start there);
 // g0 = its first block of the source attention.  Passed to the kernels by value (1 KB of kernel arguments).
 constexpr int MAX_UTT = 32, MAX_ROWS = 1024;
@@ -182,17 +177,16 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(const float* __restrict_
 // block the 480 blocks of a beam-40 step pull 98 MB through the L2s at T = 400: 35 us per launch).  Layout as dec_attn_kernel:
 // 16 lanes per key, 16 keys per block iteration, four iterations' loads in flight; wave w owns the softmax of hypothesis w.
 constexpr int SRC_HB = 4;
-// rows [b0, min(b0 + SRC_HB, n)) against `len` keys with nwv waves.  GROUPED: the block may have more waves than nwv (a launch
-// over utterances of different lengths has the block size of the longest); the spare waves only meet the barriers, so that keys are
+// rows [b0, min(b0 + SRC_HB, n)) against `len` keys with nwv waves.  The block may have more waves than nwv (a launch over
+// utterances of different lengths has the block size of the longest); the spare waves only meet the barriers, so that keys are
 // dealt to waves and partial sums are added exactly as in a launch of nwv waves.
-template <bool GROUPED>
 AVSR_DEV void src_attn_block(char* smem, float* s_l, const float* __restrict__ q, long ldq, const float* __restrict__ kv, long step_j, int voff,
                              int b0, int n, int len, int nwv, float scale, float* __restrict__ out, long ldo) {
     float* sc = reinterpret_cast<float*>(smem);  // [SRC_HB][len]
     float* part = sc + SRC_HB * len;             // [nwv][SRC_HB][64]
     const int h = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool busy = !GROUPED || wave < nwv;
+    const bool busy = wave < nwv;
     const int g = lane >> 4, c = lane & 15;
     f32x4 q4[SRC_HB];
 #pragma unroll
@@ -281,14 +275,7 @@ AVSR_DEV void src_attn_block(char* smem, float* s_l, const float* __restrict__ q
     }
 }
 
-__global__ __launch_bounds__(1024) void dec_src_attn_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ kv, long step_j,
-                                                           int voff, int n, int len, float scale, float* __restrict__ out, long ldo) {
-    AVSR_DYN_SMEM(smem);
-    __shared__ float s_l[SRC_HB];
-    src_attn_block<false>(smem, s_l, q, ldq, kv, step_j, voff, blockIdx.x * SRC_HB, n, len, blockDim.x >> 6 /* 4, 8 or 16 waves */, scale, out, ldo);
-}
-
-// The same for a group of utterances: block x belongs to the utterance whose block range [g0, ...) holds it, takes SRC_HB of ITS
+// Over the utterances of a group: block x belongs to the utterance whose block range [g0, ...) holds it, takes SRC_HB of ITS
 // rows (a block never holds rows of two utterances) against ITS memory projection kv + f0 * step_j and length, with the wave count
 // a launch for that length alone would have.  Dynamic LDS is sized for the longest utterance.
 __global__ __launch_bounds__(1024) void dec_src_attn_group_kernel(Group grp, const float* __restrict__ q, long ldq, const float* __restrict__ kv,
@@ -299,8 +286,8 @@ __global__ __launch_bounds__(1024) void dec_src_attn_group_kernel(Group grp, con
     while (u + 1 < grp.U && (int)blockIdx.x >= grp.u[u + 1].g0) u++;
     const Utt d = grp.u[u];
     const int nwv = d.T <= 64 ? 4 : (d.T <= 256 ? 8 : 16);
-    src_attn_block<true>(smem, s_l, q, ldq, kv + (size_t)d.f0 * step_j, step_j, voff, d.off + ((int)blockIdx.x - d.g0) * SRC_HB, d.off + d.n, d.T,
-                         nwv, scale, out, ldo);
+    src_attn_block(smem, s_l, q, ldq, kv + (size_t)d.f0 * step_j, step_j, voff, d.off + ((int)blockIdx.x - d.g0) * SRC_HB, d.off + d.n, d.T,
+                   nwv, scale, out, ldo);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -844,7 +831,7 @@ struct SelectArgs {
     float* selg;       // [K] gain of the selected extensions
 };
 
-// row0: the packed row of the utterance's hypothesis 0 (what `prev` counts from; 0 for a search of one utterance)
+// row0: the packed row of the utterance's hypothesis 0 (what `prev` counts from)
 AVSR_DEV void beam_select_block(char* smem, RadixScratch& sc, const SelectArgs& a, int row0) {
     const int NE = a.n * (a.S + 1);
     float* val = reinterpret_cast<float*>(smem);            // [NE]
@@ -923,12 +910,6 @@ AVSR_DEV void beam_select_block(char* smem, RadixScratch& sc, const SelectArgs& 
         a.selv[4 * rank + 2] = ctc_rel;
         a.selv[4 * rank + 3] = log_psi;
     }
-}
-
-__global__ __launch_bounds__(SEL_NT) void beam_select_kernel(SelectArgs a) {
-    AVSR_DYN_SMEM(smem);
-    __shared__ RadixScratch sc;
-    beam_select_block(smem, sc, a, 0);
 }
 
 // One block per utterance of a group on that utterance's entries: `a` describes the packed tables (row 0 of the group), the block
@@ -1014,13 +995,6 @@ AVSR_DEV void beam_update_row(const BeamBuf& src, const BeamBuf& dst, int ldy, i
     for (int i = tid; i < 2 * T; i += 256) dst_r[(size_t)i * K + kl] = r_new[((size_t)i * n_src + pl) * S + pos];
 }
 
-__global__ __launch_bounds__(256) void beam_update_kernel(BeamBuf src, BeamBuf dst, int ldy, int beam, int L, int n_src, int K, int T, int S,
-                                                          const int* __restrict__ sel, const float* __restrict__ selv,
-                                                          const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
-                                                          const float* __restrict__ selg, float* __restrict__ host_row) {
-    beam_update_row(src, dst, ldy, beam, L, n_src, K, T, S, blockIdx.x, blockIdx.x, 0, sel, selv, r_new, dst.r, lm_logp, ld_lm, selg, host_row);
-}
-
 // the utterance that owns row k of the beam being written
 AVSR_DEV int utt_of_new_row(const Group& g, int k) {
     int u = 0;
@@ -1028,7 +1002,7 @@ AVSR_DEV int utt_of_new_row(const Group& g, int k) {
     return u;
 }
 
-// group form: block = new packed row; the scalars have pitch `pitch` (the group's rows), an utterance's CTC regions the pitch
+// block = new packed row; the scalars have pitch `pitch` (the group's rows), an utterance's CTC regions the pitch
 // `beam` rows per frame: r at 2 * f0 * beam, r_new at 2 * f0 * beam * S
 __global__ __launch_bounds__(256) void beam_update_group_kernel(BeamBuf src, BeamBuf dst, Group grp, int ldy, int pitch, int beam, int L, int S,
                                                                 const int* __restrict__ sel, const float* __restrict__ selv,
@@ -1040,23 +1014,8 @@ __global__ __launch_bounds__(256) void beam_update_group_kernel(BeamBuf src, Bea
                     dst.r + (size_t)2 * d.f0 * beam, lm_logp, ld_lm, selg, host_row);
 }
 
-// hypotheses keep.idx[0 .. keep.n) survive (ended ones are taken off the beam, batch_beam_search.py:178-206)
-__global__ __launch_bounds__(256) void beam_keep_kernel(BeamBuf src, BeamBuf dst, int ldy, int beam, int L, int n_src, int T, IdxList keep) {
-    const int k = blockIdx.x, tid = threadIdx.x, from = keep.idx[k];
-    for (int j = tid; j < L; j += 256) {
-        dst.yseq[(size_t)k * ldy + j] = src.yseq[(size_t)from * ldy + j];
-        if (j < L - 1) dst.anc[(size_t)k * ldy + j] = src.anc[(size_t)from * ldy + j];
-    }
-    if (tid < 6) dst.sc[tid * beam + k] = src.sc[tid * beam + from];
-    if (tid == 6) dst.last[k] = src.last[from];
-    if (tid == 7 && src.node) {
-        dst.node[k] = src.node[from];
-        dst.bias[k] = src.bias[from];
-    }
-    for (int i = tid; i < 2 * T; i += 256) dst.r[(size_t)i * keep.n + k] = src.r[(size_t)i * n_src + from];
-}
-
-// group form: new packed row k = current packed row keep.from[k] (of the same utterance); utterance u goes from n to nn rows
+// the listed hypotheses survive (ended ones are taken off the beam, batch_beam_search.py:178-206): new packed row k = current packed
+// row keep.from[k] (of the same utterance); utterance u goes from n to nn rows
 __global__ __launch_bounds__(256) void beam_keep_group_kernel(BeamBuf src, BeamBuf dst, Group grp, int ldy, int pitch, int beam, int L, RowList keep) {
     const int k = blockIdx.x, tid = threadIdx.x, from = keep.from[k];
     const Utt d = grp.u[utt_of_new_row(grp, k)];
@@ -1076,21 +1035,7 @@ __global__ __launch_bounds__(256) void beam_keep_group_kernel(BeamBuf src, BeamB
     for (int i = tid; i < 2 * d.T; i += 256) dr[(size_t)i * d.nn + kl] = sr[(size_t)i * d.n + fl];
 }
 
-__global__ void beam_init_kernel(BeamBuf st, int beam, int T, int sos, const float* __restrict__ r_init) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid == 0) {
-        st.yseq[0] = sos;
-        st.last[0] = sos;
-        for (int i = 0; i < 6; i++) st.sc[i * beam] = 0.f;
-        if (st.node) {  // the root of the bias trie
-            st.node[0] = 0;
-            st.bias[0] = 0.f;
-        }
-    }
-    if (tid < 2 * T) st.r[tid] = r_init[tid];
-}
-
-// group form: block (x, u); utterance u starts as the one row u
+// block (x, u); utterance u starts as the one row u
 __global__ void beam_init_group_kernel(BeamBuf st, Group grp, PtrList r_init, int ldy, int pitch, int beam, int sos) {
     const int u = blockIdx.y, tid = blockIdx.x * blockDim.x + threadIdx.x;
     const Utt d = grp.u[u];
@@ -1098,7 +1043,7 @@ __global__ void beam_init_group_kernel(BeamBuf st, Group grp, PtrList r_init, in
         st.yseq[(size_t)d.off * ldy] = sos;
         st.last[d.off] = sos;
         for (int i = 0; i < 6; i++) st.sc[i * pitch + d.off] = 0.f;
-        if (st.node) {
+        if (st.node) {  // the root of the bias trie
             st.node[d.off] = 0;
             st.bias[d.off] = 0.f;
         }
@@ -1144,18 +1089,16 @@ struct Session {
     int pe_rows;
     std::vector<Layer> layers;
     const float *ang, *anb, *wout, *bout;
-    // per utterance
+    // per group of utterances (avsr_beam_begin_batch; avsr_beam_begin: a group of one): the tables carved for U * beam rows and the
+    // frames of all of them.  T: frames of the longest utterance (0: nothing begun), n: running hypotheses of all utterances
     int T = 0, Lmax = 0, ldy = 0, ldv = 0, n = 0, L = 0, cur = 0;
-    const float* ctc_logp = nullptr;
-    int ld_ctc = 0;
     BeamBuf st[2];
     std::vector<float*> cache;   // per layer [Lmax][beam][3 D]: q | k | v of the position's row
     std::vector<float*> memkv;   // per layer [T][2 D]
     float *x, *x1, *x2, *h, *att, *q2, *ff, *part, *stx, *st1, *st2, *mean, *rstd, *logits, *logp, *lse, *psi, *psi_eos, *r_new, *selv, *host_dev;
     int64_t* cand;
     int* sel;
-    // a group of utterances (avsr_beam_begin_batch): U > 0, the tables above carved for U * beam rows and the frames of all of them
-    int U = 0, Tmax = 0;
+    int U = 0;
     Utt utt[MAX_UTT];  // off / n / T / f0 of every utterance (n == 0: retired); the per-launch fields are filled by group_of
     const float* u_logp[MAX_UTT];
     int32_t u_ld[MAX_UTT];
@@ -1195,7 +1138,7 @@ struct Carver {
     }
 };
 
-// rows: hypotheses the tables hold (beam; U * beam for a group), T: frames (of all utterances of a group: the per-utterance regions
+// rows: hypotheses the tables hold (U * beam), T: frames (of all utterances of the group: the per-utterance regions
 // of the CTC state, of r_new and of the memory projection lie behind one another, `beam` rows per frame)
 void carve(Session& s, Carver& c, size_t rows, size_t T, int Lmax) {
     const size_t per = s.beam, beam = rows, D = s.D;
@@ -1499,43 +1442,10 @@ extern "C" int avsr_beam_set_bias(int64_t h, const int32_t* cfg, const float* fc
     return 0;
 }
 
-extern "C" int64_t avsr_beam_workspace_bytes(int64_t h, int T, int Lmax) {
-    Session tmp = *reinterpret_cast<Session*>((intptr_t)h);
-    Carver c{nullptr};
-    carve(tmp, c, tmp.beam, T, Lmax);
-    return (int64_t)c.off + 256;
-}
-
-// New utterance: memory [T][D] f32 (encoder output), ctc_logp [T][ld_ctc] f32 log-softmax of the CTC head, r_init [T][2] the
-// CTC state of the empty prefix (ctc_prefix_score.py:60-66).  Projects the memory's K / V for every layer, resets the beam to <sos>.
-extern "C" int avsr_beam_begin(int64_t h, const float* memory, int T, const float* ctc_logp, int ld_ctc, const float* r_init, void* ws,
-                               int64_t ws_bytes, int Lmax, hipStream_t stream) {
-    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(T >= 1 && Lmax >= 1 && Lmax + 1 <= s.pe_rows, "beam_begin: bad lengths (position table too short?)");
-    AVSR_REQUIRE(!s.lm.on || Lmax + 1 <= s.lm.pe_rows, "beam_begin: the language model's position table is too short");
-    Carver c{reinterpret_cast<char*>(ws)};
-    carve(s, c, s.beam, T, Lmax);
-    AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin: workspace too small");
-    s.bias = s.bias_next;
-    s.U = 0;
-    s.T = T;
-    s.Lmax = Lmax;
-    s.ctc_logp = ctc_logp;
-    s.ld_ctc = ld_ctc;
-    s.n = 1;
-    s.L = 1;
-    s.cur = 0;
-    for (int l = 0; l < s.nl; l++)
-        DEC_TRY(gemm(memory, s.D, s.layers[l].wkv2, T, 2 * s.D, s.D, s.layers[l].bkv2, 0, nullptr, 0, s.memkv[l], 2 * s.D, stream));
-    AVSR_LAUNCH(beam_init_kernel, dim3((2 * T + 255) / 256), dim3(256), 0, stream, s.st[0], s.beam, T, s.sos, r_init);
-    AVSR_CHECK_LAUNCH("beam_begin");
-    return 0;
-}
-
 // The decoder's pass over the new position of the n running hypotheses (rows of st), L tokens each: log-probabilities into s.logp,
-// pre-beam candidates into s.cand.  pitch: slots per position of the K / V caches (beam; the rows of a group); grp: the utterances of
-// a group (s.T = the longest one's frames), NULL for a search of one utterance.
-static int dec_pass(Session& s, BeamBuf& st, int n, int L, int pitch, const Group* grp, hipStream_t stream) {
+// pre-beam candidates into s.cand.  pitch: slots per position of the K / V caches (the rows the group's tables hold); grp: the
+// utterances of the group (s.T = the longest one's frames).
+static int dec_pass(Session& s, BeamBuf& st, int n, int L, int pitch, const Group& grp, hipStream_t stream) {
     const int D = s.D, beam = pitch;  // slots per position of the cache
     const float scale = 1.0f / sqrtf(64.f);
     if (s.lm.on) DEC_TRY(lm_step(s, st, n, L, pitch, stream));
@@ -1553,12 +1463,9 @@ static int dec_pass(Session& s, BeamBuf& st, int n, int L, int pitch, const Grou
                     (const float*)s.cache[l], (long)beam * 3 * D, (long)3 * D, D, 2 * D, (const int*)st.anc, s.ldy, L, scale, s.att, (long)D);
         DEC_TRY(skinny(s.att, D, w.wo, n, D, D, w.bo, nullptr, nullptr, 0.f, nullptr, 0, x, D, s.x1, D, &s1, nullptr, stream));
         DEC_TRY(skinny(s.x1, D, w.wq2, n, D, D, w.bq2, w.n2g, w.n2b, s.eps, &s1, 0, nullptr, 0, s.q2, D, nullptr, nullptr, stream));
-        if (grp) {  // (block size and LDS of the longest utterance; every block works with the waves of its own)
-            AVSR_LAUNCH(dec_src_attn_group_kernel, dim3(grp->blocks, s.H), dim3(64 * wv_src), (size_t)SRC_HB * (s.T + 64 * wv_src) * sizeof(float), stream,
-                        *grp, (const float*)s.q2, (long)D, (const float*)s.memkv[l], (long)2 * D, D, scale, s.att, (long)D);
-        } else
-            AVSR_LAUNCH(dec_src_attn_kernel, dim3((n + SRC_HB - 1) / SRC_HB, s.H), dim3(64 * wv_src), (size_t)SRC_HB * (s.T + 64 * wv_src) * sizeof(float), stream,
-                        (const float*)s.q2, (long)D, (const float*)s.memkv[l], (long)2 * D, D, n, s.T, scale, s.att, (long)D);
+        // (block size and LDS of the longest utterance; every block works with the waves of its own)
+        AVSR_LAUNCH(dec_src_attn_group_kernel, dim3(grp.blocks, s.H), dim3(64 * wv_src), (size_t)SRC_HB * (s.T + 64 * wv_src) * sizeof(float), stream,
+                    grp, (const float*)s.q2, (long)D, (const float*)s.memkv[l], (long)2 * D, D, scale, s.att, (long)D);
         DEC_TRY(skinny(s.att, D, w.wo2, n, D, D, w.bo2, nullptr, nullptr, 0.f, nullptr, 0, s.x1, D, s.x2, D, &s2, nullptr, stream));
         DEC_TRY(skinny(s.x2, D, w.w1, n, s.FF, D, w.b1, w.n3g, w.n3b, s.eps, &s2, 1, nullptr, 0, s.ff, s.FF, nullptr, nullptr, stream));
         DEC_TRY(skinny(s.ff, s.FF, w.w2, n, D, s.FF, w.b2, nullptr, nullptr, 0.f, nullptr, 0, s.x2, D, s.x, D, &sx, s.part, stream));
@@ -1566,75 +1473,6 @@ static int dec_pass(Session& s, BeamBuf& st, int n, int L, int pitch, const Grou
     DEC_TRY(skinny(x, D, s.wout, n, s.V, D, s.bout, s.ang, s.anb, s.eps, &sx, 0, nullptr, 0, s.logits, s.ldv, nullptr, nullptr, stream));
     AVSR_LAUNCH(logsoftmax_prebeam_kernel, dim3(n), dim3(SEL_NT), (size_t)(s.V + s.S) * sizeof(unsigned), stream, (const float*)s.logits, s.logp,
                 (long)s.ldv, s.V, s.S, s.cand);
-    return 0;
-}
-
-// One decoding step for the n running hypotheses (all of length L): decoder pass over the new position, pre-beam, CTC
-// prefix scores, top-K, new beam state.  host_out [K][8] f32: token, parent, total score, decoder / ctc / length-bonus
-// sums, language-model sum (0 without one), bias sum (0 without a list) -- valid on return (the call synchronises the stream).  Returns K through n_out.
-// With a language model attached its pass is issued first, in line on the same stream (DESIGN.md section 7).  A bias list adds no
-// launch: the selection looks the gains up where it forms the scores, the update stores the node reached.
-extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
-    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(s.U == 0, "beam_step: the session runs a group of utterances (avsr_beam_step_batch)");
-    AVSR_REQUIRE(s.n >= 1 && s.L <= s.Lmax, "beam_step: no running hypotheses / maximum length reached");
-    const int n = s.n, L = s.L, beam = s.beam;
-    BeamBuf& st = s.st[s.cur];
-    BeamBuf& nx = s.st[s.cur ^ 1];
-    DEC_TRY(dec_pass(s, st, n, L, beam, nullptr, stream));
-    DEC_TRY(avsr_ctc_prefix_score(s.ctc_logp, s.T, s.V, s.ld_ctc, st.r, st.last, s.cand, n, s.S, L - 1, s.blank, s.r_new, s.psi,
-                                  s.psi_eos, stream));
-    const int NE = n * (s.S + 1);
-    const int K = beam;  // n * V >= beam always; the viable entries n * (S - 1) >= beam by the create-time check
-    SelectArgs a{s.logp, (long)s.ldv, s.cand, s.psi, s.psi_eos, st.sc + 4 * beam, st.sc, n, s.S, K, s.eos, s.blank, s.has_len,
-                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv, s.bias.tab, st.node, s.bias.w, s.selg};
-    AVSR_LAUNCH(beam_select_kernel, dim3(1), dim3(SEL_NT), (size_t)(2 * NE + K + n * s.S + n) * 4, stream, a);
-    AVSR_LAUNCH(beam_update_kernel, dim3(K), dim3(256), 0, stream, st, nx, s.ldy, beam, L, n, K, s.T, s.S, (const int*)s.sel,
-                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, (const float*)s.selg, s.host_dev);
-    AVSR_CHECK_LAUNCH("beam_step");
-    const int e = avsr_copy_to_host_sync(host_out, s.host_dev, (size_t)K * 8 * sizeof(float), stream);
-    if (e != 0) {
-        avsr_set_error2("beam_step", hipGetErrorString((hipError_t)e));
-        return 2;
-    }
-    s.cur ^= 1;
-    s.n = K;
-    s.L = L + 1;
-    *n_out = K;
-    return 0;
-}
-
-// take the hypotheses NOT listed off the beam (keep: ascending indices into the current beam)
-extern "C" int avsr_beam_keep(int64_t h, const int32_t* keep, int n_keep, hipStream_t stream) {
-    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(s.U == 0 && n_keep >= 0 && n_keep <= s.n, "beam_keep: bad count");
-    if (n_keep == s.n) return 0;
-    if (n_keep > 0) {
-        IdxList il;
-        il.n = n_keep;
-        for (int i = 0; i < n_keep; i++) {
-            AVSR_REQUIRE(keep[i] >= 0 && keep[i] < s.n, "beam_keep: index out of range");
-            il.idx[i] = keep[i];
-        }
-        AVSR_LAUNCH(beam_keep_kernel, dim3(n_keep), dim3(256), 0, stream, s.st[s.cur], s.st[s.cur ^ 1], s.ldy, s.beam, s.L, s.n, s.T, il);
-        AVSR_CHECK_LAUNCH("beam_keep");
-        s.cur ^= 1;
-    }
-    s.n = n_keep;
-    return 0;
-}
-
-// token sequences of the current beam: host_yseq [n][ldy] int64, the first L entries of every row valid (synchronises);
-// returns the row pitch through ldy_out and the length through L_out
-extern "C" int avsr_beam_fetch_yseq(int64_t h, int64_t* host_yseq, int* ldy_out, int* L_out, hipStream_t stream) {
-    Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    const int e = avsr_copy_to_host_sync(host_yseq, s.st[s.cur].yseq, (size_t)s.n * s.ldy * sizeof(int64_t), stream);
-    if (e != 0) {
-        avsr_set_error2("beam_fetch_yseq", hipGetErrorString((hipError_t)e));
-        return 2;
-    }
-    *ldy_out = s.ldy;
-    *L_out = s.L;
     return 0;
 }
 
@@ -1672,8 +1510,10 @@ extern "C" int64_t avsr_beam_batch_workspace_bytes(int64_t h, int U, const int32
     return (int64_t)c.off + 256;
 }
 
-// New group: per utterance what avsr_beam_begin takes (arrays of length U in host memory), ONE workspace of
-// avsr_beam_batch_workspace_bytes(handle, U, T, Lmax), Lmax = the most steps any of them takes.
+// New group (arrays of length U in host memory): per utterance memory [T][D] f32 (encoder output), ctc_logp [T][ld_ctc] f32
+// log-softmax of the CTC head, r_init [T][2] the CTC state of the empty prefix (ctc_prefix_score.py:60-66); ONE workspace of
+// avsr_beam_batch_workspace_bytes(handle, U, T, Lmax), Lmax = the most steps any of them takes.  Projects every memory's K / V for
+// every layer, resets every beam to <sos>; the session takes over the bias list bound last.
 extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memory, const int32_t* T, const float* const* ctc_logp,
                                      const int32_t* ld_ctc, const float* const* r_init, void* ws, int64_t ws_bytes, int Lmax, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
@@ -1687,7 +1527,7 @@ extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memor
     AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin_batch: workspace too small");
     s.bias = s.bias_next;
     s.U = U;
-    s.T = s.Tmax = Tmax;
+    s.T = Tmax;
     s.Lmax = Lmax;
     s.n = U;
     s.L = 1;
@@ -1713,12 +1553,15 @@ extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memor
     return 0;
 }
 
-// ONE step for all running hypotheses of all running utterances: the launches of avsr_beam_step on the packed rows, one
-// device-to-host copy of [rows][8] records (utterance after utterance, the columns of avsr_beam_step; `parent` counts within the
-// utterance), one stream synchronise.  n_out [U]: records per utterance (beam; 0 for a retired one).
+// ONE step for all running hypotheses (all of length L) of all running utterances: decoder pass over the new position, pre-beam,
+// CTC prefix scores, top-K per utterance, new beam state; one device-to-host copy of [rows][8] f32 records, utterance after
+// utterance -- token, parent (counted within the utterance), total score, decoder / ctc / length-bonus sums, language-model sum (0
+// without one), bias sum (0 without a list) -- valid on return (the call synchronises the stream).  n_out [U]: records per utterance
+// (beam; 0 for a retired one: n * V >= beam always, the viable entries n * (S - 1) >= beam by the create-time check).
+// With a language model attached its pass is issued first, in line on the same stream (DESIGN.md section 7).  A bias list adds no
+// launch: the selection looks the gains up where it forms the scores, the update stores the node reached.
 extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(s.U >= 1, "beam_step_batch: no group (avsr_beam_begin_batch)");
     const int U = s.U, L = s.L, beam = s.beam, pitch = U * beam;
     int nn[MAX_UTT], off[MAX_UTT], cnt[MAX_UTT], Ts[MAX_UTT];
     int64_t f0[MAX_UTT];
@@ -1737,7 +1580,7 @@ extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipS
     }
     BeamBuf& st = s.st[s.cur];
     BeamBuf& nx = s.st[s.cur ^ 1];
-    DEC_TRY(dec_pass(s, st, n, L, pitch, &g, stream));
+    DEC_TRY(dec_pass(s, st, n, L, pitch, g, stream));
     DEC_TRY(avsr_ctc_prefix_score_batch(U, s.u_logp, Ts, s.u_ld, s.V, st.r, st.last, s.cand, off, cnt, f0, beam, s.S, L - 1, s.blank, s.r_new,
                                         s.psi, s.psi_eos, stream));
     SelectArgs a{s.logp, (long)s.ldv, s.cand, s.psi, s.psi_eos, st.sc + 4 * pitch, st.sc, 0, s.S, beam, s.eos, s.blank, s.has_len,
@@ -1755,7 +1598,7 @@ extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipS
     s.L = L + 1;
     int o = 0;
     for (int u = 0; u < U; u++) {
-        // (`parent` of a record is a packed row of the previous beam: the host sees it within the utterance, as avsr_beam_step gives it)
+        // (`parent` of a record is a packed row of the previous beam: the host sees it within the utterance)
         for (int k = 0; k < nn[u]; k++) host_out[(size_t)(o + k) * 8 + 1] -= (float)off[u];
         s.utt[u].n = nn[u];
         s.utt[u].off = o;
@@ -1770,7 +1613,6 @@ extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipS
 // that survive, n_keep [U] how many per utterance; n_keep[u] == 0 retires utterance u (it takes no further part in the steps).
 extern "C" int avsr_beam_keep_batch(int64_t h, const int32_t* keep, const int32_t* n_keep, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(s.U >= 1, "beam_keep_batch: no group (avsr_beam_begin_batch)");
     int nn[MAX_UTT];
     bool same = true;
     int total = 0;
@@ -1809,7 +1651,6 @@ extern "C" int avsr_beam_keep_batch(int64_t h, const int32_t* keep, const int32_
 // first L entries of every row valid (synchronises)
 extern "C" int avsr_beam_fetch_yseq_batch(int64_t h, int64_t* host_yseq, int* ldy_out, int* L_out, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
-    AVSR_REQUIRE(s.U >= 1, "beam_fetch_yseq_batch: no group (avsr_beam_begin_batch)");
     const int e = avsr_copy_to_host_sync(host_yseq, s.st[s.cur].yseq, (size_t)s.n * s.ldy * sizeof(int64_t), stream);
     if (e != 0) {
         avsr_set_error2("beam_fetch_yseq_batch", hipGetErrorString((hipError_t)e));
@@ -1818,4 +1659,23 @@ extern "C" int avsr_beam_fetch_yseq_batch(int64_t h, int64_t* host_yseq, int* ld
     *ldy_out = s.ldy;
     *L_out = s.L;
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// One utterance: a group of one.  The scalars of these calls are the arrays of length one of the calls above; the records, the
+// workspace size (the tables of 1 * beam rows and T frames) and the results are those calls' own.
+extern "C" int64_t avsr_beam_workspace_bytes(int64_t h, int T, int Lmax) { return avsr_beam_batch_workspace_bytes(h, 1, &T, Lmax); }
+
+extern "C" int avsr_beam_begin(int64_t h, const float* memory, int T, const float* ctc_logp, int ld_ctc, const float* r_init, void* ws,
+                               int64_t ws_bytes, int Lmax, hipStream_t stream) {
+    return avsr_beam_begin_batch(h, 1, &memory, &T, &ctc_logp, &ld_ctc, &r_init, ws, ws_bytes, Lmax, stream);
+}
+
+extern "C" int avsr_beam_step(int64_t h, float* host_out, int* n_out, hipStream_t stream) { return avsr_beam_step_batch(h, host_out, n_out, stream); }
+
+// take the hypotheses NOT listed off the beam (keep: ascending indices into the current beam)
+extern "C" int avsr_beam_keep(int64_t h, const int32_t* keep, int n_keep, hipStream_t stream) { return avsr_beam_keep_batch(h, keep, &n_keep, stream); }
+
+extern "C" int avsr_beam_fetch_yseq(int64_t h, int64_t* host_yseq, int* ldy_out, int* L_out, hipStream_t stream) {
+    return avsr_beam_fetch_yseq_batch(h, host_yseq, ldy_out, L_out, stream);
 }

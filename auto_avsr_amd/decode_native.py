@@ -4,9 +4,10 @@
 (lightning.py:126-158: this build's TransformerDecoder, CTCPrefixScorer, optionally LengthBonus, pre-beam on the decoder
 scores): same search (batch_beam_search.py:208-349 over beam_search.py:330-457), same hypotheses, with the per-step work --
 decoder pass on the new position over cached K / V, pre-beam, CTC prefix scores, top-k, beam re-ordering -- issued from C++
-(`avsr_beam_step`) instead of ~120 python-issued launches.  The python loop here only looks at the 1 KB the step copies
-back (tokens, parents, scores), collects ended hypotheses and applies the end-detection rule.  Any other scorer
-configuration keeps the python step of decoding.py."""
+(`avsr_beam_step_batch`) instead of ~120 python-issued launches.  There is ONE host loop, `NativeBeam.search_group`, for a group
+of U utterances whose running hypotheses share every step; `search` is the group of one.  The loop only looks at the 1 KB per
+utterance the step copies back (tokens, parents, scores), collects ended hypotheses and applies the end-detection rule.  Any
+other scorer configuration keeps the python step of decoding.py."""
 import contextlib
 import ctypes
 import math
@@ -181,10 +182,7 @@ class NativeBeam:
                 raise
         self.handle, self.lib, self.key, self.keep_alive = h, L, key, keep
         self.V, self.pe_rows = V, pe.shape[0]
-        pin = dev.type == "cuda"
-        self.host = torch.empty(MAX_BEAM * 8, dtype=torch.float32, pin_memory=pin)
-        self.host_np = self.host.numpy().reshape(MAX_BEAM, 8)
-        self.yseq_host = None
+        self.group_host = self.group_yseq_host = None  # pinned result buffers of search_group, sized by the largest group so far
         self.bias_key = None
         self._bind_bias(dev)
 
@@ -224,81 +222,11 @@ class NativeBeam:
     # ------------------------------------------------------------------------------------------------ the search
     @torch.no_grad()
     def search(self, x, maxlenratio=0.0, minlenratio=0.0, ctc_state=None):
-        """ctc_state: (log-posteriors [T][ld], empty-prefix state [T][2]) from `prepare_ctc` when the caller computed them (search_many)."""
-        from .decoding import Hypothesis
-
-        bs = self.bs
-        if maxlenratio == 0:
-            maxlen = x.shape[0]
-        elif maxlenratio < 0:
-            maxlen = -1 * int(maxlenratio)
-        else:
-            maxlen = max(1, int(maxlenratio * x.size(0)))
-        dev = x.device
-        dec, ctc = bs.full_scorers["decoder"], bs.part_scorers["ctc"]
-        self._bind(dev, maxlen + 2)
-        L = _lib.lib()
-        T = x.shape[0]
-        logp, r_init = ctc_state if ctc_state is not None else prepare_ctc(ctc, x)
-        memory = _f32(x)
-        nws = L.call("avsr_beam_workspace_bytes", self.handle, T, maxlen)
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        stream = ops._stream(memory)
-        L.call("avsr_beam_begin", self.handle, memory.data_ptr(), T, logp.data_ptr(), logp.stride(0), r_init.data_ptr(), ws.data_ptr(),
-               nws, maxlen, stream)
-        n_out = ctypes.c_int(0)
-        host_ptr, n_ptr = self.host.data_ptr(), ctypes.cast(ctypes.pointer(n_out), ctypes.c_void_p)
-        names = ["decoder"] + [k for k in ("lm", "bias", "length_bonus") if k in bs.full_scorers] + ["ctc"]
-        col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6, "bias": 7}
-        eos = bs.eos
-        ended, best, best_len = [], -math.inf, {}
-
-        def fetch():
-            yseq_host = self.yseq_host
-            if yseq_host is None or yseq_host.shape[0] < bs.beam_size * (maxlen + 2):
-                yseq_host = self.yseq_host = torch.empty(bs.beam_size * (maxlen + 2), dtype=torch.int64, pin_memory=dev.type == "cuda")
-            ldy, Lc = ctypes.c_int(0), ctypes.c_int(0)
-            L.call("avsr_beam_fetch_yseq", self.handle, yseq_host.data_ptr(), ctypes.cast(ctypes.pointer(ldy), ctypes.c_void_p),
-                   ctypes.cast(ctypes.pointer(Lc), ctypes.c_void_p), stream)
-            return yseq_host.numpy(), ldy.value, Lc.value
-
-        def end(row, ys, forced):
-            nonlocal best
-            ys = list(ys) + ([eos] if forced else [])
-            sc = float(row[2])
-            ended.append(Hypothesis(yseq=torch.tensor(ys, dtype=torch.int64), score=sc, scores={k: float(row[col[k]]) for k in names},
-                                    states={}))
-            best = max(best, sc)
-            best_len[len(ys)] = max(best_len.get(len(ys), -math.inf), sc)
-
-        for i in range(maxlen):
-            L.call("avsr_beam_step", self.handle, host_ptr, n_ptr, stream)
-            K = n_out.value
-            out = self.host_np[:K]
-            tok = out[:, 0].astype(np.int64)
-            if i == maxlen - 1:  # force an end so that at least one hypothesis finishes (beam_search.py:430-436)
-                ys, ldy, Lc = fetch()
-                for b in range(K):
-                    end(out[b], ys[b * ldy: b * ldy + Lc], True)
-                n_alive = 0
-            else:
-                is_eos = tok == eos
-                n_alive = K
-                if is_eos.any():
-                    ys, ldy, Lc = fetch()
-                    for b in np.nonzero(is_eos)[0].tolist():
-                        end(out[b], ys[b * ldy: b * ldy + Lc], False)
-                    keep = np.nonzero(~is_eos)[0].astype(np.int32)
-                    n_alive = int(keep.shape[0])
-                    L.call("avsr_beam_keep", self.handle, keep.ctypes.data, n_alive, stream)
-            if maxlenratio == 0.0 and ended and self._end_detect(best, best_len, i):
-                break
-            if n_alive == 0:
-                break
-        nbest = sorted(ended, key=lambda h: float(h.score), reverse=True)
-        if not nbest:
-            return [] if minlenratio < 0.1 else self.search(x, maxlenratio, max(0.0, minlenratio - 0.1), ctc_state=(logp, r_init))
-        return nbest
+        """One utterance: a group of one.  ctc_state: (log-posteriors [T][ld], empty-prefix state [T][2]) from `prepare_ctc` when the
+        caller computed them (search_many)."""
+        if ctc_state is None:
+            ctc_state = prepare_ctc(self.bs.part_scorers["ctc"], x)
+        return self.search_group([x], [ctc_state], maxlenratio, minlenratio)[0]
 
     # ------------------------------------------------------------------------------------------------ a group of utterances
     def group_workspace_bytes(self, Ts, Lmax):
@@ -311,9 +239,9 @@ class NativeBeam:
 
     @torch.no_grad()
     def search_group(self, xs, pre, maxlenratio=0.0, minlenratio=0.0):
-        """The searches of `search` for U utterances with ONE library call per step (avsr_beam_step_batch): every utterance has its
-        own maxlen, takes its forced end there, collects its own <eos> hypotheses, stops by its own end detection, and is retired
-        (n_keep = 0) while the others go on.  pre[u] = prepare_ctc of xs[u].  Returns one n-best list per utterance."""
+        """The searches of U utterances with ONE library call per step (avsr_beam_step_batch): every utterance has its own maxlen,
+        takes its forced end there, collects its own <eos> hypotheses, stops by its own end detection, and is retired (n_keep = 0)
+        while the others go on.  pre[u] = prepare_ctc of xs[u].  Returns one n-best list per utterance."""
         from .decoding import Hypothesis
 
         bs = self.bs
@@ -334,14 +262,16 @@ class NativeBeam:
                ws.data_ptr(), nws, Lmax, stream)
         rows = U * bs.beam_size
         pin = dev.type == "cuda"
-        host = getattr(self, "group_host", None)
+        host = self.group_host
         if host is None or host.shape[0] < rows * 8:
             host = self.group_host = torch.empty(rows * 8, dtype=torch.float32, pin_memory=pin)
         host_np = host.numpy().reshape(-1, 8)
-        yseq_host = getattr(self, "group_yseq_host", None)
+        yseq_host = self.group_yseq_host
         if yseq_host is None or yseq_host.shape[0] < rows * (Lmax + 2):
             yseq_host = self.group_yseq_host = torch.empty(rows * (Lmax + 2), dtype=torch.int64, pin_memory=pin)
-        n_out = i32()
+        n_out, c_ldy, c_L = i32(), ctypes.c_int(0), ctypes.c_int(0)
+        host_ptr, n_ptr = host.data_ptr(), vp(n_out)  # (what a step passes, formed once)
+        yseq_np, yseq_ptr, ldy_ptr, Lc_ptr = yseq_host.numpy(), yseq_host.data_ptr(), vp(ctypes.pointer(c_ldy)), vp(ctypes.pointer(c_L))
         names = ["decoder"] + [k for k in ("lm", "bias", "length_bonus") if k in bs.full_scorers] + ["ctc"]
         col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6, "bias": 7}
         eos = bs.eos
@@ -358,32 +288,28 @@ class NativeBeam:
             best[u] = max(best[u], sc)
             best_len[u][len(ys)] = max(best_len[u].get(len(ys), -math.inf), sc)
 
+        def fetch():
+            L.call("avsr_beam_fetch_yseq_batch", self.handle, yseq_ptr, ldy_ptr, Lc_ptr, stream)
+            return yseq_np, c_ldy.value, c_L.value
+
         for i in range(Lmax):
-            L.call("avsr_beam_step_batch", self.handle, host.data_ptr(), vp(n_out), stream)
-            counts = list(n_out)
+            L.call("avsr_beam_step_batch", self.handle, host_ptr, n_ptr, stream)
             fetched = None
-
-            def fetch():
-                ldy, Lc = ctypes.c_int(0), ctypes.c_int(0)
-                L.call("avsr_beam_fetch_yseq_batch", self.handle, yseq_host.data_ptr(), vp(ctypes.pointer(ldy)), vp(ctypes.pointer(Lc)), stream)
-                return yseq_host.numpy(), ldy.value, Lc.value
-
-            keep, n_keep, changed, off = [], [0] * U, False, 0
+            alive_of, changed, off = [()] * U, False, 0  # per utterance the rows that stay on its beam (the keep list is formed when one leaves)
             for u in range(U):
-                K = counts[u]
+                K = n_out[u]
                 if not running[u]:
                     continue
                 out = host_np[off: off + K]
-                tok = out[:, 0].astype(np.int64)
                 if i == maxlens[u] - 1:  # this utterance's forced end (beam_search.py:430-436)
                     fetched = fetched or fetch()
                     ys, ldy, Lc = fetched
                     for b in range(K):
                         end(u, out[b], ys[(off + b) * ldy: (off + b) * ldy + Lc], True)
-                    alive = []
+                    alive = ()
                 else:
-                    is_eos = tok == eos
-                    alive = list(range(K))
+                    is_eos = out[:, 0] == eos
+                    alive = range(K)
                     if is_eos.any():
                         fetched = fetched or fetch()
                         ys, ldy, Lc = fetched
@@ -391,16 +317,16 @@ class NativeBeam:
                             end(u, out[b], ys[(off + b) * ldy: (off + b) * ldy + Lc], False)
                         alive = np.nonzero(~is_eos)[0].tolist()
                 if maxlenratio == 0.0 and ended[u] and self._end_detect(best[u], best_len[u], i):
-                    alive = []
+                    alive = ()
                 if not alive:
                     running[u] = False
                 changed = changed or len(alive) != K
-                keep += alive
-                n_keep[u] = len(alive)
+                alive_of[u] = alive
                 off += K
             if not any(running):
                 break
             if changed:
+                keep, n_keep = [b for a in alive_of for b in a], [len(a) for a in alive_of]
                 L.call("avsr_beam_keep_batch", self.handle, vp((ctypes.c_int32 * max(1, len(keep)))(*keep)), vp(i32(*n_keep)), stream)
         results = []
         for u in range(U):

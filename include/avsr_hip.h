@@ -605,7 +605,6 @@ int avsr_bias_score(const int32_t* first, const int32_t* tok, const int32_t* chi
  * session that never saw this call.  All utterances of a group share the list. */
 int avsr_beam_set_bias(int64_t handle, const int32_t* cfg, const float* fcfg, const int32_t* first, const int32_t* tok,
                        const int32_t* child, const int32_t* unc);
-int64_t avsr_beam_workspace_bytes(int64_t handle, int T, int Lmax);
 /* the linear layer of a decoding step on its own: C = act(LN?(A) W^T + bias) + resid for M <= 128 rows (transformer_decoder.py:84-126
  * on one position per hypothesis); st_in [M][st_in_nt][2] per-row (sum, sum of squares) partials of A when ln_g != NULL;
  * st_out [M][ceil(N/16)][2] (may be NULL) the same for the rows of C, partial count per row through st_out_nt; partial: scratch of
@@ -618,6 +617,8 @@ int avsr_decode_linear(const float* A, int lda, const float* W, int M, int N, in
  * anc_scratch: n * len ints of scratch */
 int avsr_decode_attention(const float* q, int ldq, const float* kv, int64_t step_b, int64_t step_j, int koff, int voff, int n, int H,
                           int len, float* out, int ldo, int32_t* anc_scratch, avsr_stream_t stream);
+/* ---- ONE utterance = the group calls below with U = 1, for a session begun by avsr_beam_begin (after _begin_batch: n_out [U]) */
+int64_t avsr_beam_workspace_bytes(int64_t handle, int T, int Lmax);
 /* new utterance: memory [T][D] f32 encoder output, ctc_logp [T][ld_ctc] f32 log-softmax of the CTC head, r_init [T][2] CTC
  * state of the empty prefix (ctc_prefix_score.py:60-66), workspace of avsr_beam_workspace_bytes(handle, T, Lmax) */
 int avsr_beam_begin(int64_t handle, const float* memory, int T, const float* ctc_logp, int ld_ctc, const float* r_init,
@@ -629,23 +630,22 @@ int avsr_beam_step(int64_t handle, float* host_out, int* n_out, avsr_stream_t st
 int avsr_beam_keep(int64_t handle, const int32_t* keep, int n_keep, avsr_stream_t stream);
 /* token sequences of the current beam into host_yseq [n][*ldy_out] (first *L_out entries of a row valid); synchronises */
 int avsr_beam_fetch_yseq(int64_t handle, int64_t* host_yseq, int* ldy_out, int* L_out, avsr_stream_t stream);
-/* ---- the same search for a GROUP of utterances per step (the reference runs batch_beam_search.py:208-349 once per utterance; the
- * searches are independent, so one label-synchronous step can serve U of them).  Same handle, bound weights and language model as
- * above.  The running hypotheses of all utterances form one packed row list, utterance after utterance, all at the same position;
- * 1 <= U <= 32 and U * beam <= 1024 rows, larger groups are refused.  A session runs either one utterance or one group at a time.
- * Arrays of length U are host memory. */
-/* workspace of a group with frame counts T[U] and at most Lmax steps (0 and avsr_last_error for a group that is refused): the
- * tables of avsr_beam_workspace_bytes sized for U * beam rows (per layer a [Lmax][U * beam][3 D] cache, the language model's too) and
- * for the frames of all utterances (memory K / V, CTC state and r_new regions behind one another) */
+/* ---- the search for a GROUP of utterances per step: the implementation (the reference runs batch_beam_search.py:208-349 once per
+ * utterance; the searches are independent, so one label-synchronous step can serve U of them).  The running hypotheses of all
+ * utterances form one packed row list, utterance after utterance, all at the same position; 1 <= U <= 32 and U * beam <= 1024 rows,
+ * larger groups are refused.  A session runs one group at a time; every begin starts a new one.  Arrays of length U: host memory. */
+/* workspace of a group with frame counts T[U] and at most Lmax steps (0 and avsr_last_error for a group that is refused): tables
+ * of U * beam rows (per layer a [Lmax][U * beam][3 D] cache, the language model's too) and of the frames of all utterances (memory
+ * K / V, CTC state and r_new regions behind one another) */
 int64_t avsr_beam_batch_workspace_bytes(int64_t handle, int U, const int32_t* T, int Lmax);
-/* avsr_beam_begin for every utterance u: memory[u] [T[u]][D], ctc_logp[u] [T[u]][ld_ctc[u]], r_init[u] [T[u]][2]; projects every
+/* new group, per utterance what avsr_beam_begin takes: memory[u] [T[u]][D], ctc_logp[u] [T[u]][ld_ctc[u]], r_init[u] [T[u]][2]; projects every
  * memory's K / V, resets every beam to <sos>; Lmax = the most steps any of them takes */
 int avsr_beam_begin_batch(int64_t handle, int U, const float* const* memory, const int32_t* T, const float* const* ctc_logp,
                           const int32_t* ld_ctc, const float* const* r_init, void* workspace, int64_t workspace_bytes, int Lmax,
                           avsr_stream_t stream);
-/* one step (beam_search.py:330-406) for all running hypotheses of all running utterances: the launches of avsr_beam_step on the packed
- * rows, ONE device-to-host copy of [rows][8] records (the columns of avsr_beam_step, utterance after utterance, parent counted within
- * the utterance), ONE stream synchronise; n_out [U]: records of every utterance (0: retired) */
+/* one step (beam_search.py:330-406) for all running hypotheses of all running utterances on the packed rows, ONE device-to-host
+ * copy of [rows][8] records (the columns of avsr_beam_step, utterance after utterance, parent counted within the utterance), ONE
+ * stream synchronise; n_out [U]: records of every utterance (0: retired) */
 int avsr_beam_step_batch(int64_t handle, float* host_out, int* n_out, avsr_stream_t stream);
 /* drop hypotheses (batch_beam_search.py:178-206 per utterance): keep = utterance after utterance the ascending indices within that
  * utterance's beam that stay, n_keep [U] their counts; n_keep[u] == 0 retires utterance u (beam_search.py:430-446: its search is over) */
