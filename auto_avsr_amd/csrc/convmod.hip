@@ -103,6 +103,81 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, co
     }
 }
 
+// stage_time_tile_glu for an utterance that holds only `len` <= Tlen frames of its Tlen-frame slot: frames at or beyond `len` are
+// staged as zeros -- selected, never multiplied, so whatever the padded rows of `a` hold (NaN included) stays out of the window.
+template <class T>
+AVSR_DEV void stage_time_tile_glu_len(float* xs, const T* a, int b, int t_first, int nrows, int Tlen, int len, int C, int c0) {
+    for (int id = threadIdx.x; id < nrows * (DW_CH / 8); id += 256) {
+        const int r = id / (DW_CH / 8), cc = (id % (DW_CH / 8)) * 8;
+        const int t = t_first + r;
+        float v[8], g[8];
+        if (t >= 0 && t < len && c0 + cc < C) {
+            const T* row = a + ((long)b * Tlen + t) * 2 * C + c0 + cc;
+            load8(row, v);
+            load8(row + C, g);
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                v[e] *= avsr_sigmoid(g[e]);
+                v[e] = round_as_stored<T>(v[e]);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++) v[e] = 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) xs[r * DW_CH + cc + e] = v[e];
+    }
+}
+
+// Inference middle of the ConvolutionModule on a zero-padded batch (conformer_encoder.py:32-34 with eval-mode BatchNorm):
+//   s[b,t,:] = silu(gamma * (dwconv(glu(a[b, 0..len_b-1, :]))[t] - mean) * invstd + beta)   for t <  len_b = lens[b]
+//   s[b,t,:] = 0                                                                              for t >= len_b
+// dwconv_kernel's tile (64 channels x 32 outputs, window and taps in LDS, fixed 31-tap loop, same accumulation order) with the
+// utterance's own length as the convolution's edge and bn_act_fwd_kernel's expression as the epilogue.  The reference convolves
+// over the padded frames too (conformer_encoder.py:30-35 masks nothing); they are non-zero after LayerNorm and the pointwise
+// bias and would leak into the last K/2 valid frames of every shorter utterance.  TY: storage type of s (f16 for an f32 chain
+// in the mixed mode: rounded once, here).
+template <class T, class TY>
+__global__ __launch_bounds__(256) void dw_eval_kernel(const T* __restrict__ a, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, const int* __restrict__ lens,
+                                                      TY* __restrict__ s, int Tlen, int C, int K,
+                                                      const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta) {
+    __shared__ float xs[(DW_TT + DW_MAXK - 1) * DW_CH];
+    __shared__ float ws[DW_MAXK * DW_CH];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int c0 = blockIdx.x * DW_CH, t0 = blockIdx.y * DW_TT, b = blockIdx.z;
+    const int pad = (K - 1) / 2;
+    const int len = lens ? min(max(lens[b], 0), Tlen) : Tlen;
+    const bool cok = c0 + tx < C;
+    if (t0 >= len) {  // (block-uniform) the whole time tile is padding: zeros, nothing staged
+#pragma unroll
+        for (int o = 0; o < DW_TT / 4; o++) {
+            const int t = t0 + ty * (DW_TT / 4) + o;
+            if (t < Tlen && cok) Elem<TY>::st(s + ((long)b * Tlen + t) * C + c0 + tx, 0.f);
+        }
+        return;
+    }
+    stage_time_tile_glu_len<T>(xs, a, b, t0 - pad, DW_TT + DW_MAXK - 1, Tlen, len, C, c0);
+    for (int k = ty; k < DW_MAXK; k += 4) ws[k * DW_CH + tx] = (k < K && cok) ? w[(long)(c0 + tx) * K + k] : 0.f;
+    __syncthreads();
+    const float bv = (bias && cok) ? bias[c0 + tx] : 0.f;
+    const float mu = cok ? mean[c0 + tx] : 0.f, is = cok ? invstd[c0 + tx] : 0.f;
+    const float ga = cok ? gamma[c0 + tx] : 0.f, be = cok ? beta[c0 + tx] : 0.f;
+#pragma unroll
+    for (int o = 0; o < DW_TT / 4; o++) {
+        const int t = ty * (DW_TT / 4) + o;
+        float acc = bv;
+#pragma unroll
+        for (int k = 0; k < DW_MAXK; k++) acc += ws[k * DW_CH + tx] * xs[(t + k) * DW_CH + tx];
+        if (t0 + t < Tlen && cok) {
+            acc = round_as_stored<T>(acc);  // the depthwise output the stand-alone sequence stores before its BatchNorm pass
+            const float z = (acc - mu) * is * ga + be;
+            Elem<TY>::st(s + ((long)b * Tlen + t0 + t) * C + c0 + tx, t0 + t < len ? avsr_silu(z) : 0.f);
+        }
+    }
+}
+
 // dw[c,k] += sum_{b,t} dy[b,t,c] x[b,t+k-pad,c] ;  db[c] += sum dy
 // A block owns EIGHT channels x all taps: thread = (tap lane k = 0..31, channel 0..7); lane 31 carries the bias sum.  It walks
 // every gridDim.y-th (batch element, 256-step time tile) pair: the tile's dy rows and x rows (+ K - 1 halo) are fetched into
@@ -226,6 +301,28 @@ extern "C" int avsr_dwconv_fwd2(const float* x, const float* w, const float* bia
     AVSR_LAUNCH((dwconv_kernel<float>), grid, block, 0, stream, x, w, bias, y, T, C, K, 0, glu_in, (const float*)nullptr,
                 (bf16_t*)y2);
     AVSR_CHECK_LAUNCH("dwconv_fwd2");
+    return 0;
+}
+
+extern "C" int avsr_convmod_dw_eval_fwd(const void* a, int in_dtype, const float* wdw, const float* bdw, const int* lens, int B, int T,
+                                        int C, int K, const float* mean, const float* invstd, const float* gamma,
+                                        const float* beta, void* s, int out_dtype, hipStream_t stream) {
+    AVSR_REQUIRE(K >= 1 && K <= DW_MAXK && (K & 1), "convmod_dw_eval: K must be odd and <= 31");
+    AVSR_REQUIRE(C % 8 == 0, "convmod_dw_eval: C must be a multiple of 8");
+    AVSR_REQUIRE((in_dtype == 0 && (out_dtype == 0 || out_dtype == 2)) || (in_dtype == 1 && out_dtype == 1),
+                 "convmod_dw_eval: f32 -> f32, f32 -> f16 or bf16 -> bf16");
+    if (B <= 0 || T <= 0) return 0;
+    dim3 grid((C + DW_CH - 1) / DW_CH, (T + DW_TT - 1) / DW_TT, B), block(256);
+    if (in_dtype == 1)
+        AVSR_LAUNCH((dw_eval_kernel<bf16_t, bf16_t>), grid, block, 0, stream, (const bf16_t*)a, wdw, bdw, lens, (bf16_t*)s, T, C, K,
+                    mean, invstd, gamma, beta);
+    else if (out_dtype == 2)
+        AVSR_LAUNCH((dw_eval_kernel<float, f16_t>), grid, block, 0, stream, (const float*)a, wdw, bdw, lens, (f16_t*)s, T, C, K, mean,
+                    invstd, gamma, beta);
+    else
+        AVSR_LAUNCH((dw_eval_kernel<float, float>), grid, block, 0, stream, (const float*)a, wdw, bdw, lens, (float*)s, T, C, K, mean,
+                    invstd, gamma, beta);
+    AVSR_CHECK_LAUNCH("convmod_dw_eval_fwd");
     return 0;
 }
 

@@ -327,6 +327,35 @@ def numerics(mode_name):
         _restore_mode(old)
 
 
+@contextlib.contextmanager
+def padded_lengths(lens, module=None):
+    """Evaluation of a zero-padded batch: inside, the Conformer convolution module runs its depthwise convolution over frames
+    0 .. lens[b]-1 of utterance b only (ops.convmod_dw_eval), so that together with the attention key mask a padded batch encodes
+    what each utterance encodes alone.  lens: the B lengths (a tensor or a sequence); kept as an int32 tensor, moved once to the
+    activations' device -- nothing is derived from the mask on the host.  Inference only: `module` (optional), when given, must not
+    be in training mode, and a convolution sub-layer that meets the context while training fails its assertion."""
+    assert module is None or not module.training, "padded_lengths: evaluation only (the module is in training mode)"
+    assert _state.get("pad_lens") is None, "padded_lengths: already entered"
+    lens = torch.as_tensor(lens).to(torch.int32).contiguous()
+    assert lens.dim() == 1
+    _state["pad_lens"] = lens
+    try:
+        yield lens
+    finally:
+        _state["pad_lens"] = None
+
+
+def _padded_lens_for(x, B):
+    """The lengths of padded_lengths() on x's device (None outside the context)."""
+    lens = _state.get("pad_lens")
+    if lens is None:
+        return None
+    assert lens.numel() == B, f"padded_lengths: {lens.numel()} lengths for a batch of {B}"
+    if lens.device != x.device:
+        lens = _state["pad_lens"] = lens.to(x.device)
+    return lens
+
+
 def act_dtype():
     return torch.float32 if _state["precise"] else (torch.float16 if _state["f16"] else torch.bfloat16)
 

@@ -135,6 +135,19 @@ class ConvSublayerFn(torch.autograd.Function):
         # a[:, :D] * sigmoid(a[:, D:]) on the fly, the GLU output is never written
         gl = None
         wdw = w_dw.view(D, K)
+        lens = AF._padded_lens_for(x, B)
+        if lens is not None:
+            # evaluation of a zero-padded batch (AF.padded_lengths): GLU, the depthwise convolution over each utterance's own frames,
+            # eval-mode BatchNorm and Swish in one launch; the mixed mode's f32 chain is rounded to f16 on the way out.  Forward only.
+            assert not training, "padded_lengths: evaluation only (the convolution module is in training mode)"
+            assert not torch.is_grad_enabled(), "padded_lengths: no autograd through the length-exact path (use torch.no_grad())"
+            bmean, binv = ops.bn_eval_params(bn_rm, bn_rv, bn_eps)
+            s = ops.convmod_dw_eval(a, wdw, b_dw, lens, B, Tn, D, K, bmean, binv, bn_w, bn_b, out_dtype=T if Tc != T else None)
+            po, so, sdo = _drop_args(p_out, x)  # (p_out is 0 in evaluation)
+            y = torch.empty_like(x)
+            _gemm_nt(s, w_pw2.view(D, D), rows, D, D, y, bias=b_pw2, drop_p=po, seed=so, seed_dev=sdo,
+                     resid=x if fused else None, ldr=D)
+            return y
         one_launch = training and AF._BN_SMALL and _state["bn_sync"] is None and rows <= ops.BN_SMALL_MAX_ROWS
         # round 6 experiment (AVSR_CONVMOD_FUSED=1, off by default: slower, functional.py _CONVMOD_FUSED): the whole element-wise
         # middle (GLU, depthwise conv, BatchNorm statistics + running stats + normalise, Swish) as ONE launch -- a block owns 8
@@ -226,6 +239,8 @@ def conv_sublayer(x, ln_w, ln_b, w_pw1, b_pw1, w_dw, b_dw, bn, w_pw2, b_pw2, p_o
     """bn: the torch.nn.BatchNorm1d module holding weight / bias / running stats (updated in place in training).
     ln_w = ln_b = None gives the bare module (no LayerNorm, no residual, no output dropout)."""
     training = bn.training
+    assert not (training and _state.get("pad_lens") is not None), \
+        "padded_lengths: evaluation only (the convolution module is in training mode)"
     _state["tag_ok"] = torch.is_grad_enabled()
     momentum = bn.momentum if bn.momentum is not None else 0.1
     # the batch counter of the BatchNorm is incremented by its statistics kernel (bn_finalize)

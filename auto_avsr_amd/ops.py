@@ -447,6 +447,23 @@ def convmod_dwbn_bwd(a, c, ds, mean, invstd, gamma, beta, wdw, B, T, C, K, dwdw,
     return da, dgamma, dbeta
 
 
+def convmod_dw_eval(a, wdw, bdw, lens, B, T, C, K, mean, invstd, gamma, beta, out_dtype=None):
+    """Inference middle of the ConvolutionModule on a zero-padded batch in ONE launch: a [B*T, 2C] -> GLU -> depthwise conv over
+    frames 0 .. lens[b]-1 of utterance b only -> BatchNorm (mean / invstd of bn_eval_params) -> SiLU -> s [B*T, C]; rows at or beyond
+    lens[b] are zeros.  lens: int32 [B] on a's device, None = every utterance has T frames.  out_dtype (f32 input only):
+    torch.float16 -- the f32 chain is rounded once on the way out."""
+    out_dtype = out_dtype or a.dtype
+    assert (a.dtype, out_dtype) in ((torch.float32, torch.float32), (torch.float32, torch.float16),
+                                    (torch.bfloat16, torch.bfloat16)), (a.dtype, out_dtype)
+    assert a.is_contiguous() and a.numel() == B * T * 2 * C
+    if lens is not None:
+        assert lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous() and lens.device == a.device
+    s = torch.empty(B * T, C, dtype=out_dtype, device=a.device)
+    call("avsr_convmod_dw_eval_fwd", _ptr(a), dt(a), _ptr(wdw), _ptr(bdw), _ptr(lens), B, T, C, K, _ptr(mean), _ptr(invstd),
+         _ptr(gamma), _ptr(beta), _ptr(s), _DT[out_dtype], _stream(a), nbytes=_nb(a, s))
+    return s
+
+
 def bn_finalize(stats, counts, world, C, eps, momentum, running_mean, running_var, num_batches_tracked=None,
                 stats_stride=0, counts_stride=0, n_total=None):
     """counts: tensor or raw device address of the first count."""

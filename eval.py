@@ -33,6 +33,11 @@ def parse_args(argv=None):
                    help="decode groups of up to N utterances of similar length with ONE decoding step per group (the batched native "
                         "beam search; utterances are taken in windows of 4 N); 0 = off.  Not with --decode-workers > 1 or "
                         "--decode-mode rescore")
+    p.add_argument("--encode-batch", type=int, default=0, metavar="N",
+                   help="run front-end and encoder on zero-padded groups of up to N utterances of similar length (length-exact: the "
+                        "convolution modules convolve over each utterance's own frames, so the encoder outputs are those of the "
+                        "one-at-a-time loop; utterances are taken in windows of 4 N); 0 = off.  Video only.  Combines with every "
+                        "other decoding flag")
     p.add_argument("--timestamps", type=str, default=None, metavar="PATH",
                    help="write one JSON line per utterance with the word timestamps of its hypothesis (CTC forced alignment on the "
                         "device, 40 ms per encoder frame): {utt, hyp, score, words: [{word, start, end}] or null}")
@@ -53,6 +58,11 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.decode_batch < 0:
         p.error("--decode-batch must be >= 0")
+    if args.encode_batch < 0:
+        p.error("--encode-batch must be >= 0")
+    if args.encode_batch > 1 and args.modality == "audio":
+        p.error("--encode-batch is video only: the audio front-end's 1-D ResNet trunk normalises and convolves across time in "
+                "every block and would need each utterance's length at every layer")
     if args.decode_batch > 1 and args.decode_workers > 1:
         p.error("--decode-batch and --decode-workers > 1 are two ways of decoding several utterances at once: choose one")
     if args.decode_batch > 1 and args.decode_mode == "rescore":
@@ -62,11 +72,13 @@ def parse_args(argv=None):
     return args
 
 
-def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps=None, decode_batch=0):
+def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps=None, decode_batch=0, encode_batch=0):
     """Trainer.test without Lightning: the module's own hooks over the loader (lightning.py:69-84,116-123).  decode_workers > 1:
     utterances are taken in groups whose beam searches run concurrently (ModelModule.decode_many); same transcripts, same WER.
     decode_batch > 1: utterances are taken in windows of 4 * decode_batch whose searches share their decoding steps in groups of
     at most decode_batch utterances of similar length; same transcripts, same WER.
+    encode_batch > 1: the grouped branch as well (windows of 4 * the largest of the three); front-end and encoder run on zero-padded
+    groups of at most encode_batch utterances (ModelModule.encode_many), the searches as the other two arguments say.
     timestamps: path of a JSON-lines file that receives, per utterance, the word timestamps of its hypothesis (CTC forced
     alignment on the encoder output the decoding already computed); without it nothing is aligned."""
     import json
@@ -79,7 +91,7 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps
     records = [] if timestamps else None
     module.timestamp_records = records  # test_step appends to it
     with torch.no_grad():
-        if decode_workers <= 1 and decode_batch <= 1:
+        if decode_workers <= 1 and decode_batch <= 1 and encode_batch <= 1:
             for i, sample in enumerate(loader):
                 sample = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in sample.items()}
                 module.test_step(sample, i)
@@ -91,7 +103,7 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps
             def flush():
                 nonlocal done
                 for s, predicted in zip(group, module.decode_many([s["input"] for s in group], workers=decode_workers, records=records,
-                                                                   batch=decode_batch)):
+                                                                   batch=decode_batch, encode_batch=encode_batch)):
                     actual = module.text_transform.post_process(s["target"])
                     module.total_edit_distance += compute_word_level_distance(actual, predicted)
                     module.total_length += len(actual.split())
@@ -102,7 +114,7 @@ def run_test_loop(module, loader, device, log=None, decode_workers=1, timestamps
 
             for sample in loader:
                 group.append({k: (v.to(device) if torch.is_tensor(v) else v) for k, v in sample.items()})
-                if len(group) == 4 * (decode_batch if decode_batch > 1 else decode_workers):
+                if len(group) == 4 * max(decode_batch, decode_workers, encode_batch):
                     flush()
             if group:
                 flush()
@@ -148,7 +160,7 @@ def cli_main(argv=None):
     else:
         loader = datamodule.test_dataloader()
     wer = run_test_loop(module, loader, torch.device("cuda"), decode_workers=args.decode_workers, timestamps=args.timestamps,
-                        decode_batch=args.decode_batch,
+                        decode_batch=args.decode_batch, encode_batch=args.encode_batch,
                         log=lambda i, d, n: logging.info(f"utt {i}: running WER {d / max(n, 1):.4f} ({d}/{n} words)"))
     print(f"WER {wer:.4f} over {module.total_length} reference words")
     return wer

@@ -147,6 +147,16 @@ int avsr_dwconv_fwd2(const float* x, const float* w, const float* bias, float* y
 /* dw[c,k] += sum dy[b,t,c] x[b,t+k-pad,c]; db[c] += sum dy; glu_in = 1: x is the pre-GLU tensor [B*T, 2C] */
 int avsr_dwconv_wgrad(const void* x, const void* dy, int dtype, float* dw, float* db, int B, int T, int C,
                       int K, int glu_in, avsr_stream_t stream);
+/* Inference middle of the ConvolutionModule on a zero-padded batch, one launch: a [B*T, 2C] (the pointwise-1 output) -> GLU ->
+ * depthwise Conv1d(K odd <= 31, weights wdw [C][K], bias bdw or NULL) over frames 0 .. lens[b]-1 of utterance b ONLY (frames at or
+ * beyond lens[b] count as zero input, as the convolution's own padding does; whatever the padded rows of a hold, NaN included,
+ * reaches no valid row) -> BatchNorm with the given mean / invstd / gamma / beta [C] (avsr_bn_eval_params) -> SiLU -> s [B*T, C];
+ * rows at or beyond lens[b] are written as zeros.  lens: int32 [B] on the device, values clamped to 0 .. T; NULL = every
+ * utterance has T frames.  (in_dtype, out_dtype): (0, 0) f32 -> f32; (0, 2) f32 chain rounded to f16 once on the way out;
+ * (1, 1) bf16 with the roundings of avsr_dwconv_fwd(glu_in) + avsr_bn_act_fwd.  No frame's arithmetic depends on T. */
+int avsr_convmod_dw_eval_fwd(const void* a, int in_dtype, const float* wdw, const float* bdw, const int* lens, int B, int T, int C,
+                             int K, const float* mean, const float* invstd, const float* gamma, const float* beta, void* s,
+                             int out_dtype, avsr_stream_t stream);
 
 /* ---- training-mode BatchNorm (+SiLU, + residual add) on channels-last [rows, C] ------------------- */
 int64_t avsr_bn_workspace_floats(int C);

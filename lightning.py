@@ -222,16 +222,65 @@ class ModelModule(_Base):
         words, score = self.align_encoded(enc_feat, token_ids)
         return {"hyp": text, "score": score, "words": words}
 
-    def decode_many(self, samples, workers=4, records=None, batch=0):
+    def encode_many(self, samples, batch=0, max_frames=None):
+        """Not in the reference: the encoder outputs (T_i, D) of several utterances, in the order of `samples`, each a contiguous
+        tensor of its own.  batch <= 1: front-end / encoder one utterance at a time, unpadded, as in `_decode`.  batch > 1
+        (video only): utterances are sorted by length and taken greedily in groups of at most `batch` while B * Tmax stays within
+        `max_frames` (default: args.max_frames, else 1600, the training bound; an utterance longer than that forms a group of its
+        own); a group is zero-padded to Tmax and runs front-end -> proj_encoder -> encoder ONCE, under the attention key mask and
+        auto_avsr_amd.functional.padded_lengths -- the convolution modules then convolve over each utterance's own frames only,
+        so every utterance is encoded as it is alone (the reference's masked padded forward is not: its depthwise convolution
+        reads the padded frames, conformer_encoder.py:30-35)."""
+        if batch <= 1:
+            encs = []
+            for sample in samples:
+                x = self.model.proj_encoder(self.model.frontend(sample.unsqueeze(0)))
+                enc_feat, _ = self.model.encoder(x, None)
+                encs.append(enc_feat.squeeze(0))
+            return encs
+        if self.modality == "audio":
+            raise NotImplementedError(
+                "encode_many(batch > 1) is video only: the audio front-end's 1-D ResNet trunk normalises and then convolves across "
+                "time in every block, so padded frames stop being zero after its first BatchNorm and the trunk would need each "
+                "utterance's length at every layer")
+        from auto_avsr_amd import functional as AF
+        from auto_avsr_amd.nets import non_pad_mask_device
+
+        if max_frames is None:
+            max_frames = getattr(getattr(self, "args", None), "max_frames", None) or 1600
+        order = sorted(range(len(samples)), key=lambda i: samples[i].shape[0])
+        groups, cur = [], []
+        for i in order:  # ascending lengths: the newcomer is the group's Tmax
+            if cur and (len(cur) == batch or (len(cur) + 1) * samples[i].shape[0] > max_frames):
+                groups.append(cur)
+                cur = []
+            cur.append(i)
+        if cur:
+            groups.append(cur)
+        encs = [None] * len(samples)
+        with torch.no_grad():
+            for g in groups:
+                lens = [int(samples[i].shape[0]) for i in g]
+                tmax = max(lens)
+                x = samples[g[0]].new_zeros((len(g), tmax) + tuple(samples[g[0]].shape[1:]))
+                for b, i in enumerate(g):
+                    x[b, :lens[b]] = samples[i]
+                lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
+                mask = non_pad_mask_device(lens_dev, tmax)
+                with AF.padded_lengths(lens_dev, self.model):
+                    h = self.model.proj_encoder(self.model.frontend(x))
+                    enc, _ = self.model.encoder(h, mask)
+                for b, i in enumerate(g):
+                    encs[i] = enc[b, :lens[b]].clone()
+        return encs
+
+    def decode_many(self, samples, workers=4, records=None, batch=0, encode_batch=0):
         """Not in the reference: the transcripts of several utterances, their beam searches running concurrently (one host
         thread + stream + decoding session per worker, BatchBeamSearch.forward_many) or, with batch > 1, sharing their decoding
         steps in groups of at most `batch` utterances (BatchBeamSearch.forward_batch); front-end / encoder one utterance at a
-        time, unpadded, as in `_decode`.  records: a list that receives one word-timestamp record per utterance (eval.py --timestamps)."""
-        encs = []
-        for sample in samples:
-            x = self.model.proj_encoder(self.model.frontend(sample.unsqueeze(0)))
-            enc_feat, _ = self.model.encoder(x, None)
-            encs.append(enc_feat.squeeze(0))
+        time, unpadded, as in `_decode`, or with encode_batch > 1 in zero-padded groups of at most that many utterances
+        (encode_many).  records: a list that receives one word-timestamp record per utterance (eval.py --timestamps)."""
+        encs = self.encode_many(samples, batch=encode_batch)
         out = []
         nbests = self.beam_search.forward_batch(encs, batch=batch) if batch > 1 else self.beam_search.forward_many(encs, workers=workers)
         for enc, nbest in zip(encs, nbests):

@@ -45,11 +45,18 @@ def main():
                          "(precise mode; python tools/bench_decode.py --bias > profiles/context_bias_decode.json).  With --two-pass: two-pass "
                          "decoding without and with the same list, alternated -- first pass and whole decode "
                          "(python tools/bench_decode.py --two-pass --bias > profiles/two_pass_bias_decode.json)")
+    ap.add_argument("--encode", action="store_true",
+                    help="encoder-only rows instead of the default ones: 16 utterances around T = 100 and around T = 400 frames (lengths spread "
+                         "+-20 %) through ModelModule.encode_many one at a time and in zero-padded groups of 4, 8 and 16, alternated, precise "
+                         "and mixed modes, then a whole --decode-mode rescore decode without and with encode_batch 16 "
+                         "(python tools/bench_decode.py --encode > profiles/encode_batch.json)")
     ap.add_argument("--bias-weight", type=float, default=1.0, help="--two-pass --bias: the weight of the list")
     ap.add_argument("--rescore-beam", type=int, default=16)
     ap.add_argument("--rescore-topk", type=int, default=16)
     ap.add_argument("--modes", type=str, default="precise", help="--two-pass: comma-separated numerical modes (eval.py decodes in precise)")
     args = ap.parse_args()
+    if args.encode:
+        return main_encode(args)
     if args.lm:
         return main_lm(args)
     if args.two_pass_sweep:
@@ -358,6 +365,126 @@ def main_two_pass(args):
     print(json.dumps({"metric": "two-pass decoding (CTC prefix beam search on the device + teacher-forced rescoring) against the native one-call "
                                 "hybrid search, video E2E 250M, vocabulary 5049, search only (encoder output ready)",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def main_encode(args):
+    """Encoder side of evaluation alone: front-end -> proj_encoder -> 12 Conformer layers, one utterance at a time (B = 1, unpadded)
+    against length-exact zero-padded groups (ModelModule.encode_many); the sides alternate inside every repetition."""
+    import statistics
+
+    import lightning
+    from synth import synth_state_dict
+
+    from auto_avsr_amd import decoding
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+
+    dev = torch.device("cuda:0")
+    m = E2E(5049, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    toks = [str(i) for i in range(5049)]
+
+    class Text:
+        token_list = toks
+
+        def post_process(self, ids):
+            return " ".join(str(int(i)) for i in ids if int(i) != -1)
+
+    mod = lightning.ModelModule.__new__(lightning.ModelModule)
+    torch.nn.Module.__init__(mod)
+    mod.modality, mod.model, mod.text_transform, mod.token_list = "video", m, Text(), toks
+    mod.args = argparse.Namespace(decode_mode="rescore", rescore_beam=args.rescore_beam, rescore_topk=args.rescore_topk)
+    decoding.NATIVE_BEAM = True
+    N = 16
+
+    def utterances(T):
+        g = torch.Generator().manual_seed(T)
+        lens = [round(T * (0.8 + 0.4 * i / (N - 1))) for i in range(N)]  # T - 20 % .. T + 20 %
+        lens = [lens[i] for i in torch.randperm(N, generator=g).tolist()]
+        return lens, [torch.randn(n, 1, 88, 88, generator=g).to(dev) for n in lens]
+
+    def groups_of(lens, batch, max_frames=1600):  # the groups encode_many forms (sizes only)
+        sizes, cur = [], 0
+        for n in sorted(lens):
+            if cur and (cur == batch or (cur + 1) * n > max_frames):
+                sizes.append(cur)
+                cur = 0
+            cur += 1
+        return sizes + [cur]
+
+    def stats(ts):
+        return {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    rows = []
+    sides = (1, 4, 8, 16)
+    for mode in ("precise", "mixed"):
+        AF.set_mode(mode)
+        AF.invalidate_weight_cache()
+        for T in (100, 400):
+            lens, samples = utterances(T)
+            ts = {b: [] for b in sides}
+            worst = {b: 0.0 for b in sides}
+            for rep in range(args.reps + 1):
+                base = None
+                for b in sides:  # alternated: every repetition visits every side
+                    t, encs = timed(lambda: mod.encode_many(samples, batch=b))
+                    if rep:
+                        ts[b].append(t)
+                        continue
+                    if b == 1:  # warm-up repetition: the sides must agree
+                        base = [e.double() for e in encs]
+                    else:
+                        worst[b] = max(float((e.double() - r).norm() / r.norm()) for e, r in zip(encs, base))
+                        assert worst[b] < 1e-3, (mode, T, b, worst[b])
+            for b in sides:
+                rows.append({"what": "encoder only", "mode": mode, "T_frames_nominal": T, "lengths_min_max": [min(lens), max(lens)],
+                             "utterances": N, "encode_batch": b, "groups": [1] * N if b == 1 else groups_of(lens, b),
+                             "ms_for_all": stats(ts[b]),
+                             "utterances_per_sec": {k: round(N / (v / 1e3), 2) for k, v in
+                                                    (("median", statistics.median(ts[b])), ("min", max(ts[b])), ("max", min(ts[b])))},
+                             "speedup_over_one_at_a_time_medians": round(statistics.median(ts[1]) / statistics.median(ts[b]), 3),
+                             "max_rel_l2_against_one_at_a_time": None if b == 1 else float(f"{worst[b]:.3g}")})
+                print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+            del samples
+    # the whole decode of eval.py --decode-mode rescore (precise): ModelModule.decode_many without and with encode_batch 16
+    AF.set_mode("precise")
+    AF.invalidate_weight_cache()
+    mod.beam_search = mod._make_beam_search()
+    for T in (100, 400):
+        lens, samples = utterances(T)
+        ts, hyps = {0: [], 16: []}, {}
+        for rep in range(args.reps + 1):
+            for eb in (0, 16):
+                t, out = timed(lambda: mod.decode_many(samples, workers=1, encode_batch=eb))
+                if rep:
+                    ts[eb].append(t)
+                else:
+                    hyps[eb] = out
+        for eb in (0, 16):
+            rows.append({"what": "whole decode, --decode-mode rescore", "mode": "precise", "T_frames_nominal": T, "utterances": N,
+                         "encode_batch": eb, "rescore_beam": args.rescore_beam, "rescore_topk": args.rescore_topk, "ms_for_all": stats(ts[eb]),
+                         "utterances_per_sec_median": round(N / (statistics.median(ts[eb]) / 1e3), 2),
+                         "speedup_over_encode_batch_0_medians": round(statistics.median(ts[0]) / statistics.median(ts[eb]), 3),
+                         "hypotheses_equal_encode_batch_0": sum(a == b for a, b in zip(hyps[eb], hyps[0]))})
+            print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+        del samples
+    AF.set_mode("bf16")
+    print(json.dumps({"metric": "encoder side of evaluation (front-end + proj_encoder + 12 Conformer layers) alone: one utterance at a time "
+                                "(B = 1, unpadded) against length-exact zero-padded groups (ModelModule.encode_many, max_frames 1600), video E2E "
+                                "250M; then the whole two-pass decode without and with encode_batch 16",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights; 16 utterances per row, lengths spread +-20 % around T",
+                      "timing": f"wall time between device synchronisations; sides alternated inside each of {args.reps} repetitions after one "
+                                "warm-up repetition; median [min, max]",
+                      "rows": rows}, indent=1))
 
 
 def main_batch(args):
