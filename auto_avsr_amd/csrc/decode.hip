@@ -35,7 +35,24 @@ static inline int avsr_copy_to_host_sync(void* dst, const void* src, size_t n, h
     memcpy(dst, src, n);
     return 0;
 }
+// a second result of a step, copied ahead of avsr_copy_to_host_sync on the same stream (that call's synchronisation covers it)
+static inline int avsr_copy_to_host_async(void* dst, const void* src, size_t n, hipStream_t) {
+    memcpy(dst, src, n);
+    return 0;
+}
+static inline float* avsr_host_floats(size_t n) { return static_cast<float*>(malloc(n * sizeof(float))); }
+static inline void avsr_host_floats_free(float* p) { free(p); }
 #else
+static inline int avsr_copy_to_host_async(void* dst, const void* src, size_t n, hipStream_t s) {
+    return (int)hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s);
+}
+static inline float* avsr_host_floats(size_t n) {  // page-locked, so that the copy above does not wait on the host
+    void* p = nullptr;
+    return hipHostMalloc(&p, n * sizeof(float), hipHostMallocDefault) == hipSuccess ? static_cast<float*>(p) : nullptr;
+}
+static inline void avsr_host_floats_free(float* p) {
+    if (p) (void)hipHostFree(p);
+}
 static inline int avsr_copy_to_host_sync(void* dst, const void* src, size_t n, hipStream_t s) {
     hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -760,7 +777,8 @@ __global__ __launch_bounds__(SEL_NT) void logsoftmax_prebeam_kernel(const float*
 // reach a beam of K <= n * (S - 1) -- the host refuses configurations where it could).  Arithmetic order as the python
 // form: ((w_dec * logp [+ w_lm * lm_logp] + w_len) + w_ctc * (log_psi - s_prev)) + score, f32; the language model's term
 // (shallow fusion, scorers["lm"]) only with a session that carries one, then, with a bias list, + w_bias * gain (the order of the
-// python step over the full scorers: decoder, lm, bias, length_bonus).  ONE block: radix select of the
+// python step over the full scorers: decoder, lm, bias, length_bonus); with an n-gram model + w_ngram * log p_ngram after the CTC
+// term (the partial scorers in their listed order: ctc, ngram), before the hypothesis' score.  ONE block: radix select of the
 // K best values, then a rank sort of those K (value descending, entry ascending).
 // ---------------------------------------------------------------------------------------------------------------------
 // Contextual biasing (auto_avsr_amd/bias.py: ContextBiasScorer): a trie of phrases in CSR form -- node s owns the edges
@@ -813,6 +831,76 @@ __global__ __launch_bounds__(256) void bias_score_kernel(BiasTab t, const int* _
     next[i] = nx;
 }
 
+// Back-off n-gram language model (auto_avsr_amd/ngram.py: NgramScorer), a PARTIAL scorer: a node is a context (an n-gram of order
+// < N, node 0 the empty one) that owns the edges [first[s], first[s + 1]) with tokens tok[] ascending, log-probabilities logp[] and
+// next[] = the node of the extended context; bow[s] is the node's back-off weight, back[s] the node of its longest proper suffix
+// that is a node.  A hypothesis carries one node.
+struct NgramTab {
+    const int *first, *tok;
+    const float* logp;
+    const int* next;
+    const float* bow;
+    const int* back;
+    int n_nodes;  // 0: no model
+};
+
+// edge of node s on token v, -1 if there is none.  The root of NgramScorer's tables holds the tokens 1 .. V - 1 in order, so its edge
+// on v is tried at its place first: one load instead of a 13-step search at the node every back-off chain ends at.
+AVSR_DEV int ngram_edge(const NgramTab& t, int s, int v) {
+    int lo = t.first[s], hi = t.first[s + 1];
+    if (s == 0) {
+        const int g = lo + v - 1;
+        if (g >= lo && g < hi && t.tok[g] == v) return g;
+    }
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int x = t.tok[mid];
+        if (x == v) return mid;
+        if (x < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return -1;
+}
+
+// log p(v | node s) by ARPA back-off and the node reached: walk s, back[s], ... to the first node with an edge e on v; logp[e] if
+// that is s itself, else r = bow[s0]; r += bow[s1]; ...; r += logp[e] (f32, this order: ngram.py's host lookup adds alike).  The
+// blank scores 0 and keeps the node.  The walk is cut after AVSR_NGRAM_MAX_ORDER hops (tables are not validated: a cycle in back[]
+// must not hang the step); a token without an edge at the root gets the back-offs alone.
+AVSR_DEV float ngram_logp(const NgramTab& t, int s, int v, int blank, int& next) {
+    next = s;
+    if (v == blank) return 0.f;
+    int e = ngram_edge(t, s, v);
+    if (e >= 0) {
+        next = t.next[e];
+        return t.logp[e];
+    }
+    float r = t.bow[s];
+    for (int hop = 0; s != 0 && hop < AVSR_NGRAM_MAX_ORDER; hop++) {
+        s = t.back[s];
+        e = ngram_edge(t, s, v);
+        if (e >= 0) {
+            next = t.next[e];
+            return r + t.logp[e];
+        }
+        r += t.bow[s];
+    }
+    next = 0;
+    return r;
+}
+
+// the lookup on its own (avsr_ngram_score): entry (row, c) of score / next [n][S + 1], column S = <eos>
+__global__ __launch_bounds__(256) void ngram_score_kernel(NgramTab t, const int* __restrict__ node, const int64_t* __restrict__ cand, int n, int S,
+                                                          int eos, int blank, float* __restrict__ score, int* __restrict__ next) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)n * (S + 1)) return;
+    const int row = (int)(i / (S + 1)), c = (int)(i - (long)row * (S + 1));
+    float r = 0.f;
+    int nx = 0;
+    if (t.n_nodes > 0) r = ngram_logp(t, node[row], c < S ? (int)cand[(size_t)row * S + c] : eos, blank, nx);
+    score[i] = r;
+    next[i] = nx;
+}
+
 struct SelectArgs {
     const float* logp;  // [n][ld] decoder log-probabilities
     long ld;
@@ -829,6 +917,11 @@ struct SelectArgs {
     const int* node;   // [n] trie node of every hypothesis
     float w_bias;
     float* selg;       // [K] gain of the selected extensions
+    NgramTab ng;         // n-gram model: the tables, n_nodes == 0 without one
+    const int* ng_node;  // [n] the model's node of every hypothesis
+    float w_ng;
+    float* selng;  // [K] the model's log-probability of the selected extensions
+    int* selnn;    // [K] the node they reach
 };
 
 // row0: the packed row of the utterance's hypothesis 0 (what `prev` counts from)
@@ -875,6 +968,10 @@ AVSR_DEV void beam_select_block(char* smem, RadixScratch& sc, const SelectArgs& 
             }
             if (a.has_len) w = w + a.w_len;
             w = w + a.w_ctc * ctc_rel;
+            if (a.ng.n_nodes) {  // a partial scorer after the CTC term, the order of the python step
+                int nx;
+                w = w + a.w_ng * ngram_logp(a.ng, a.ng_node[b], tok, a.blank, nx);
+            }
             v = w + a.score[b];
             if (!(v == v)) v = -INFINITY;
         }
@@ -905,6 +1002,11 @@ AVSR_DEV void beam_select_block(char* smem, RadixScratch& sc, const SelectArgs& 
         int nx = 0;
         if (a.bias.n_nodes) a.selg[rank] = (float)bias_gain(a.bias, a.node[b], tok, nx);
         a.sel[4 * rank + 3] = nx;
+        if (a.ng.n_nodes) {
+            int nn;
+            a.selng[rank] = ngram_logp(a.ng, a.ng_node[b], tok, a.blank, nn);
+            a.selnn[rank] = nn;
+        }
         a.selv[4 * rank + 0] = v;
         a.selv[4 * rank + 1] = dec;
         a.selv[4 * rank + 2] = ctc_rel;
@@ -933,6 +1035,11 @@ __global__ __launch_bounds__(SEL_NT) void beam_select_group_kernel(SelectArgs a,
         a.node += d.off;
         a.selg += d.noff;
     }
+    if (a.ng.n_nodes) {
+        a.ng_node += d.off;
+        a.selng += d.noff;
+        a.selnn += d.noff;
+    }
     beam_select_block(smem, sc, a, d.off);
 }
 
@@ -946,6 +1053,16 @@ struct BeamBuf {
     float* r;       // [T][2][n] (pitch = current n)
     int* node;      // [beam] trie node of the bias list, NULL without one
     float* bias;    // [beam] running sum of the bias gains, NULL without a list
+    int* ng_node;   // [beam] node of the n-gram model, NULL without one
+    float* ng_sum;  // [beam] running sum of the model's log-probabilities, NULL without one
+};
+
+// what the n-gram model adds to the update of a step: log-probabilities and nodes of the selected entries, the running sums of the
+// new beam for the host (avsr_beam_ngram_sums); all NULL without a model
+struct NgramSel {
+    const float* selng;
+    const int* selnn;
+    float* host_sum;
 };
 
 // new hypothesis k = hypothesis prev[k] extended by tok[k]  (batch_beam_search.py:131-176 merge + select states)
@@ -954,7 +1071,7 @@ struct BeamBuf {
 AVSR_DEV void beam_update_row(const BeamBuf& src, const BeamBuf& dst, int ldy, int beam, int L, int n_src, int K, int T, int S, int k, int kl,
                               int row0, const int* __restrict__ sel, const float* __restrict__ selv, const float* __restrict__ r_new,
                               float* __restrict__ dst_r, const float* __restrict__ lm_logp, long ld_lm, const float* __restrict__ selg,
-                              float* __restrict__ host_row) {
+                              float* __restrict__ host_row, const NgramSel& ng) {
     const int tid = threadIdx.x;
     const int prev = sel[4 * k], tok = sel[4 * k + 1], pl = prev - row0;
     int pos = sel[4 * k + 2];
@@ -990,6 +1107,10 @@ AVSR_DEV void beam_update_row(const BeamBuf& src, const BeamBuf& dst, int ldy, i
             dst.bias[k] = s_bias = src.bias[prev] + selg[k];
         }
         h[7] = s_bias;
+        if (dst.ng_node) {  // as the bias: the node the select kernel found for (prev, tok), the running f32 sum
+            dst.ng_node[k] = ng.selnn[k];
+            ng.host_sum[k] = dst.ng_sum[k] = src.ng_sum[prev] + ng.selng[k];
+        }
     }
     // CTC forward variables of (prev, candidate column pos): r_new [T][2][n_src][S] -> dst.r [T][2][K]
     for (int i = tid; i < 2 * T; i += 256) dst_r[(size_t)i * K + kl] = r_new[((size_t)i * n_src + pl) * S + pos];
@@ -1007,11 +1128,11 @@ AVSR_DEV int utt_of_new_row(const Group& g, int k) {
 __global__ __launch_bounds__(256) void beam_update_group_kernel(BeamBuf src, BeamBuf dst, Group grp, int ldy, int pitch, int beam, int L, int S,
                                                                 const int* __restrict__ sel, const float* __restrict__ selv,
                                                                 const float* __restrict__ r_new, const float* __restrict__ lm_logp, long ld_lm,
-                                                                const float* __restrict__ selg, float* __restrict__ host_row) {
+                                                                const float* __restrict__ selg, float* __restrict__ host_row, NgramSel ng) {
     const int k = blockIdx.x;
     const Utt d = grp.u[utt_of_new_row(grp, k)];
     beam_update_row(src, dst, ldy, pitch, L, d.n, d.nn, d.T, S, k, k - d.noff, d.off, sel, selv, r_new + (size_t)2 * d.f0 * beam * S,
-                    dst.r + (size_t)2 * d.f0 * beam, lm_logp, ld_lm, selg, host_row);
+                    dst.r + (size_t)2 * d.f0 * beam, lm_logp, ld_lm, selg, host_row, ng);
 }
 
 // the listed hypotheses survive (ended ones are taken off the beam, batch_beam_search.py:178-206): new packed row k = current packed
@@ -1029,6 +1150,10 @@ __global__ __launch_bounds__(256) void beam_keep_group_kernel(BeamBuf src, BeamB
         dst.node[k] = src.node[from];
         dst.bias[k] = src.bias[from];
     }
+    if (tid == 8 && src.ng_node) {
+        dst.ng_node[k] = src.ng_node[from];
+        dst.ng_sum[k] = src.ng_sum[from];
+    }
     const float* sr = src.r + (size_t)2 * d.f0 * beam;
     float* dr = dst.r + (size_t)2 * d.f0 * beam;
     const int kl = k - d.noff, fl = from - d.off;
@@ -1036,7 +1161,7 @@ __global__ __launch_bounds__(256) void beam_keep_group_kernel(BeamBuf src, BeamB
 }
 
 // block (x, u); utterance u starts as the one row u
-__global__ void beam_init_group_kernel(BeamBuf st, Group grp, PtrList r_init, int ldy, int pitch, int beam, int sos) {
+__global__ void beam_init_group_kernel(BeamBuf st, Group grp, PtrList r_init, int ldy, int pitch, int beam, int sos, int ng_start) {
     const int u = blockIdx.y, tid = blockIdx.x * blockDim.x + threadIdx.x;
     const Utt d = grp.u[u];
     if (tid == 0) {
@@ -1046,6 +1171,10 @@ __global__ void beam_init_group_kernel(BeamBuf st, Group grp, PtrList r_init, in
         if (st.node) {  // the root of the bias trie
             st.node[d.off] = 0;
             st.bias[d.off] = 0.f;
+        }
+        if (st.ng_node) {  // the n-gram model's node of <s>
+            st.ng_node[d.off] = ng_start;
+            st.ng_sum[d.off] = 0.f;
         }
     }
     if (tid < 2 * d.T) st.r[(size_t)2 * d.f0 * beam + tid] = r_init.p[u][tid];
@@ -1079,10 +1208,22 @@ struct Bias {
     float w = 0.f;
 };
 
+// The n-gram model a session may carry (avsr_beam_set_ngram): device tables owned by the caller.
+struct Ngram {
+    NgramTab tab{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    int start = 0;  // node of <s>
+    float w = 0.f;
+};
+
 struct Session {
     Lm lm;
     Bias bias, bias_next;  // the list of the running utterance / group; the list the next avsr_beam_begin* takes over
     float* selg = nullptr;
+    Ngram ng, ng_next;  // likewise the n-gram model
+    float *selng = nullptr, *ng_host_dev = nullptr;  // [rows] log-probabilities of the selected entries, running sums of the new beam
+    int* selnn = nullptr;                            // [rows] nodes the selected entries reach
+    float* ng_host = nullptr;  // [MAX_ROWS] host copy of the sums of the last step (allocated with the first model, page-locked)
+    int ng_host_n = 0;         // entries of it that are valid
     int D, H, FF, V, nl, beam, S, sos, eos, blank, has_len;
     float w_dec, w_ctc, w_len, emb_scale, eps;
     const float *embed, *pe;
@@ -1188,6 +1329,16 @@ void carve(Session& s, Carver& c, size_t rows, size_t T, int Lmax) {
         s.st[i].bias = s.bias_next.tab.n_nodes ? c.take<float>(beam) : nullptr;
     }
     s.selg = s.bias_next.tab.n_nodes ? c.take<float>(beam) : nullptr;
+    // an n-gram model, on the same terms: per-row node and running sum, log-probability and node of the selected entries, the sums
+    // of the new beam for the host
+    const bool ng = s.ng_next.tab.n_nodes != 0;
+    for (int i = 0; i < 2; i++) {
+        s.st[i].ng_node = ng ? c.take<int>(beam) : nullptr;
+        s.st[i].ng_sum = ng ? c.take<float>(beam) : nullptr;
+    }
+    s.selng = ng ? c.take<float>(beam) : nullptr;
+    s.selnn = ng ? c.take<int>(beam) : nullptr;
+    s.ng_host_dev = ng ? c.take<float>(beam) : nullptr;
     if (s.lm.on) {
         Lm& m = s.lm;
         const size_t Dl = m.D;
@@ -1368,6 +1519,7 @@ extern "C" int64_t avsr_beam_create(const int32_t* cfg, const float* fcfg, const
 extern "C" int avsr_beam_destroy(int64_t h) {
     Session* s = reinterpret_cast<Session*>((intptr_t)h);
     if (s) lm_release(s->lm);
+    if (s) avsr_host_floats_free(s->ng_host);
     delete s;
     return 0;
 }
@@ -1439,6 +1591,61 @@ extern "C" int avsr_beam_set_bias(int64_t h, const int32_t* cfg, const float* fc
         b.w = fcfg[0];
     }
     sp->bias_next = b;
+    return 0;
+}
+
+// The n-gram lookup on its own (tests, the python-issued step's cross-check): row r stands at node[r]; entry (r, c) of score / next
+// [n][S + 1] is log p of extending it by cand[r][c] (c < S) or by <eos> (c = S) and the node reached; the blank scores 0 and keeps
+// the node.  n_nodes == 0 (no model): zeros.  The tables are device memory in the layout of `struct NgramTab`; they are not validated.
+extern "C" int avsr_ngram_score(const int32_t* first, const int32_t* tok, const float* logp, const int32_t* next_tab, const float* bow,
+                                const int32_t* back, int n_nodes, int n_edges, const int32_t* node, const int64_t* cand, int n, int S, int eos,
+                                int blank, float* score, int32_t* next, hipStream_t stream) {
+    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_NGRAM_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_NGRAM_MAX_EDGES,
+                 "ngram_score: too many nodes or edges (AVSR_NGRAM_MAX_NODES / AVSR_NGRAM_MAX_EDGES)");
+    AVSR_REQUIRE(n >= 1 && S >= 0 && (int64_t)n * (S + 1) <= ((int64_t)1 << 30), "ngram_score: bad sizes");
+    const NgramTab t{first, tok, logp, next_tab, bow, back, n_edges > 0 ? n_nodes : 0};
+    AVSR_REQUIRE(t.n_nodes == 0 || (first && tok && logp && next_tab && bow && back), "ngram_score: missing table");
+    const long total = (long)n * (S + 1);
+    AVSR_LAUNCH(ngram_score_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, t, node, cand, n, S, eos, blank, score, next);
+    AVSR_CHECK_LAUNCH("ngram_score");
+    return 0;
+}
+
+// Bind an n-gram model to a session (shallow fusion, scorers["ngram"] / weights["ngram"]), or replace / remove the one it has:
+// cfg: n_nodes, n_edges (either 0: no model), start_node (the node of <s>); fcfg: weight.  The lifetime rules of avsr_beam_set_bias:
+// any time after avsr_beam_create, as often as wanted; the model takes effect at the next avsr_beam_begin / avsr_beam_begin_batch (a
+// running utterance keeps the one it began with, whose tables must stay alive until then), and the workspace sizes reported from now
+// on are those of a session with the new model.
+extern "C" int avsr_beam_set_ngram(int64_t h, const int32_t* cfg, const float* fcfg, const int32_t* first, const int32_t* tok, const float* logp,
+                                   const int32_t* next_tab, const float* bow, const int32_t* back) {
+    Session* sp = reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(sp != nullptr, "beam_set_ngram: no session");
+    const int n_nodes = cfg[0], n_edges = cfg[1], start = cfg[2];
+    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_NGRAM_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_NGRAM_MAX_EDGES,
+                 "beam_set_ngram: too many nodes or edges (AVSR_NGRAM_MAX_NODES / AVSR_NGRAM_MAX_EDGES)");
+    Ngram m;
+    if (n_nodes > 0 && n_edges > 0) {
+        AVSR_REQUIRE(first && tok && logp && next_tab && bow && back, "beam_set_ngram: missing table");
+        AVSR_REQUIRE(start >= 0 && start < n_nodes, "beam_set_ngram: the start node is not a node");
+        AVSR_REQUIRE(fcfg[0] - fcfg[0] == 0.f, "beam_set_ngram: the weight is not a finite number");
+        if (!sp->ng_host) sp->ng_host = avsr_host_floats(MAX_ROWS);
+        AVSR_REQUIRE(sp->ng_host != nullptr, "beam_set_ngram: no host memory for the running sums");
+        m.tab = NgramTab{first, tok, logp, next_tab, bow, back, n_nodes};
+        m.start = start;
+        m.w = fcfg[0];
+    }
+    sp->ng_next = m;
+    return 0;
+}
+
+// The n-gram running sums of the records of the last avsr_beam_step / avsr_beam_step_batch, in the packed order of the records: out
+// [*n_out] (at most U * beam).  Read from a host copy made inside the step's own synchronisation; *n_out = 0 without a model.
+extern "C" int avsr_beam_ngram_sums(int64_t h, float* out, int* n_out) {
+    Session* sp = reinterpret_cast<Session*>((intptr_t)h);
+    AVSR_REQUIRE(sp != nullptr && out != nullptr && n_out != nullptr, "beam_ngram_sums: no session / no output");
+    const int n = sp->ng.tab.n_nodes ? sp->ng_host_n : 0;
+    if (n > 0) memcpy(out, sp->ng_host, (size_t)n * sizeof(float));
+    *n_out = n;
     return 0;
 }
 
@@ -1526,6 +1733,8 @@ extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memor
     carve(s, c, (size_t)U * s.beam, frames, Lmax);
     AVSR_REQUIRE((int64_t)c.off <= ws_bytes, "beam_begin_batch: workspace too small");
     s.bias = s.bias_next;
+    s.ng = s.ng_next;
+    s.ng_host_n = 0;
     s.U = U;
     s.T = Tmax;
     s.Lmax = Lmax;
@@ -1548,7 +1757,7 @@ extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memor
         f0 += T[u];
     }
     const Group g = group_of(s, ones);
-    AVSR_LAUNCH(beam_init_group_kernel, dim3((2 * Tmax + 255) / 256, U), dim3(256), 0, stream, s.st[0], g, ri, s.ldy, U * s.beam, s.beam, s.sos);
+    AVSR_LAUNCH(beam_init_group_kernel, dim3((2 * Tmax + 255) / 256, U), dim3(256), 0, stream, s.st[0], g, ri, s.ldy, U * s.beam, s.beam, s.sos, s.ng.start);
     AVSR_CHECK_LAUNCH("beam_begin_batch");
     return 0;
 }
@@ -1559,7 +1768,9 @@ extern "C" int avsr_beam_begin_batch(int64_t h, int U, const float* const* memor
 // without one), bias sum (0 without a list) -- valid on return (the call synchronises the stream).  n_out [U]: records per utterance
 // (beam; 0 for a retired one: n * V >= beam always, the viable entries n * (S - 1) >= beam by the create-time check).
 // With a language model attached its pass is issued first, in line on the same stream.  A bias list adds no
-// launch: the selection looks the gains up where it forms the scores, the update stores the node reached.
+// launch: the selection looks the gains up where it forms the scores, the update stores the node reached.  Nor does an n-gram
+// model: its back-off lookups run in the selection too; the running sums of the K records go to the session's own host buffer
+// (avsr_beam_ngram_sums) by a copy issued ahead of the records' copy, under the same synchronisation -- the records stay [K][8].
 extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipStream_t stream) {
     Session& s = *reinterpret_cast<Session*>((intptr_t)h);
     const int U = s.U, L = s.L, beam = s.beam, pitch = U * beam;
@@ -1584,11 +1795,21 @@ extern "C" int avsr_beam_step_batch(int64_t h, float* host_out, int* n_out, hipS
     DEC_TRY(avsr_ctc_prefix_score_batch(U, s.u_logp, Ts, s.u_ld, s.V, st.r, st.last, s.cand, off, cnt, f0, beam, s.S, L - 1, s.blank, s.r_new,
                                         s.psi, s.psi_eos, stream));
     SelectArgs a{s.logp, (long)s.ldv, s.cand, s.psi, s.psi_eos, st.sc + 4 * pitch, st.sc, 0, s.S, beam, s.eos, s.blank, s.has_len,
-                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv, s.bias.tab, st.node, s.bias.w, s.selg};
+                 s.w_dec, s.w_ctc, s.w_len, s.lm.on ? s.lm.logp : nullptr, s.lm.w, s.sel, s.selv, s.bias.tab, st.node, s.bias.w, s.selg,
+                 s.ng.tab, st.ng_node, s.ng.w, s.selng, s.selnn};
     AVSR_LAUNCH(beam_select_group_kernel, dim3(U), dim3(SEL_NT), (size_t)(2 * n_max * (s.S + 1) + beam + n_max * s.S + n_max) * 4, stream, a, g);
     AVSR_LAUNCH(beam_update_group_kernel, dim3(K), dim3(256), 0, stream, st, nx, g, s.ldy, pitch, beam, L, s.S, (const int*)s.sel,
-                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, (const float*)s.selg, s.host_dev);
+                (const float*)s.selv, (const float*)s.r_new, (const float*)(s.lm.on ? s.lm.logp : nullptr), (long)s.ldv, (const float*)s.selg, s.host_dev,
+                NgramSel{s.selng, s.selnn, s.ng_host_dev});
     AVSR_CHECK_LAUNCH("beam_step_batch");
+    if (s.ng.tab.n_nodes) {  // the sums of the K records, into the session's own host buffer ahead of the records' copy and its sync
+        const int ec = avsr_copy_to_host_async(s.ng_host, s.ng_host_dev, (size_t)K * sizeof(float), stream);
+        if (ec != 0) {
+            avsr_set_error2("beam_step_batch", hipGetErrorString((hipError_t)ec));
+            return 2;
+        }
+        s.ng_host_n = K;
+    }
     const int e = avsr_copy_to_host_sync(host_out, s.host_dev, (size_t)K * 8 * sizeof(float), stream);
     if (e != 0) {
         avsr_set_error2("beam_step_batch", hipGetErrorString((hipError_t)e));

@@ -69,8 +69,16 @@ class NativeBeam:
         from .nets import TransformerDecoder
 
         full, part = bs.full_scorers, bs.part_scorers
-        if set(part) != {"ctc"} or not isinstance(part["ctc"], CTCPrefixScorer):
+        if set(part) not in ({"ctc"}, {"ctc", "ngram"}) or not isinstance(part["ctc"], CTCPrefixScorer):
             return False
+        if "ngram" in part:  # n-gram shallow fusion: this build's back-off scorer over the search's vocabulary, nothing else in that slot
+            from .ngram import NgramScorer
+
+            if not isinstance(part["ngram"], NgramScorer) or part["ngram"].n_vocab != bs.n_vocab:
+                return False
+            # the selection adds the CTC term, then the n-gram's: the python step adds the partial scorers in their listed order
+            if list(part) != ["ctc", "ngram"]:
+                return False
         if "decoder" not in full or not isinstance(full["decoder"], TransformerDecoder):
             return False
         if set(full) - {"decoder", "length_bonus", "lm", "bias"}:
@@ -127,6 +135,7 @@ class NativeBeam:
             key += (lm_pe.data_ptr(), lm_pe.shape[0], float(bs.weights["lm"]))
         if key == self.key:
             self._bind_bias(dev)
+            self._bind_ngram(dev)
             return
         L = _lib.lib()
         if self.handle:
@@ -185,6 +194,27 @@ class NativeBeam:
         self.group_host = self.group_yseq_host = None  # pinned result buffers of search_group, sized by the largest group so far
         self.bias_key = None
         self._bind_bias(dev)
+        self.ngram_key = None
+        self._bind_ngram(dev)
+
+    def _bind_ngram(self, dev):
+        """The model of scorers["ngram"] (avsr_beam_set_ngram), on the terms of `_bind_bias`: re-sent when the model's version or its
+        weight changed, or the session is new; detached when the scorer left the search."""
+        sc = self.bs.part_scorers.get("ngram")
+        vp = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+        if sc is None:
+            if getattr(self, "ngram_key", None) is not None:
+                self.lib.call("avsr_beam_set_ngram", self.handle, vp((ctypes.c_int32 * 3)(0, 0, 0)), vp((ctypes.c_float * 1)(0.0)),
+                              None, None, None, None, None, None)
+                self.ngram_key, self.ngram_keep = None, None
+            return
+        key = (id(sc), sc.version, float(self.bs.weights["ngram"]), str(dev))
+        if key == self.ngram_key:
+            return
+        tabs = sc.device_tables(dev)
+        self.lib.call("avsr_beam_set_ngram", self.handle, vp((ctypes.c_int32 * 3)(sc.n_nodes, sc.n_edges, sc.start_node)),
+                      vp((ctypes.c_float * 1)(self.bs.weights["ngram"])), *[t.data_ptr() for t in tabs])
+        self.ngram_key, self.ngram_keep = key, tabs  # (the tables stay alive as long as the session may read them)
 
     def _bind_bias(self, dev):
         """The bias list of scorers["bias"] (avsr_beam_set_bias): re-sent when the list's version or its weight changed, or the
@@ -274,22 +304,32 @@ class NativeBeam:
         yseq_np, yseq_ptr, ldy_ptr, Lc_ptr = yseq_host.numpy(), yseq_host.data_ptr(), vp(ctypes.pointer(c_ldy)), vp(ctypes.pointer(c_L))
         names = ["decoder"] + [k for k in ("lm", "bias", "length_bonus") if k in bs.full_scorers] + ["ctc"]
         col = {"decoder": 3, "ctc": 4, "length_bonus": 5, "lm": 6, "bias": 7}
+        # the n-gram sums of a step's records are not a column of them (the records stay [K][8]): avsr_beam_ngram_sums, packed alike
+        ngram = "ngram" in bs.part_scorers
+        ng_np = np.zeros(rows, dtype=np.float32)
+        ng_ptr, ng_n = ng_np.ctypes.data, ctypes.c_int(0)
+        ng_n_ptr = vp(ctypes.pointer(ng_n))
         eos = bs.eos
         ended = [[] for _ in range(U)]
         best = [-math.inf] * U
         best_len = [{} for _ in range(U)]
         running = [True] * U
 
-        def end(u, row, ys, forced):
+        def end(u, r, ys, forced):
+            row = host_np[r]
             ys = list(ys) + ([eos] if forced else [])
             sc = float(row[2])
-            ended[u].append(Hypothesis(yseq=torch.tensor(ys, dtype=torch.int64), score=sc, scores={k: float(row[col[k]]) for k in names},
-                                       states={}))
+            scores = {k: float(row[col[k]]) for k in names}
+            if ngram:
+                scores["ngram"] = float(ng_np[r])
+            ended[u].append(Hypothesis(yseq=torch.tensor(ys, dtype=torch.int64), score=sc, scores=scores, states={}))
             best[u] = max(best[u], sc)
             best_len[u][len(ys)] = max(best_len[u].get(len(ys), -math.inf), sc)
 
         def fetch():
             L.call("avsr_beam_fetch_yseq_batch", self.handle, yseq_ptr, ldy_ptr, Lc_ptr, stream)
+            if ngram:  # (a host copy the step made: no device work)
+                L.call("avsr_beam_ngram_sums", self.handle, ng_ptr, ng_n_ptr)
             return yseq_np, c_ldy.value, c_L.value
 
         for i in range(Lmax):
@@ -305,7 +345,7 @@ class NativeBeam:
                     fetched = fetched or fetch()
                     ys, ldy, Lc = fetched
                     for b in range(K):
-                        end(u, out[b], ys[(off + b) * ldy: (off + b) * ldy + Lc], True)
+                        end(u, off + b, ys[(off + b) * ldy: (off + b) * ldy + Lc], True)
                     alive = ()
                 else:
                     is_eos = out[:, 0] == eos
@@ -314,7 +354,7 @@ class NativeBeam:
                         fetched = fetched or fetch()
                         ys, ldy, Lc = fetched
                         for b in np.nonzero(is_eos)[0].tolist():
-                            end(u, out[b], ys[(off + b) * ldy: (off + b) * ldy + Lc], False)
+                            end(u, off + b, ys[(off + b) * ldy: (off + b) * ldy + Lc], False)
                         alive = np.nonzero(~is_eos)[0].tolist()
                 if maxlenratio == 0.0 and ended[u] and self._end_detect(best[u], best_len[u], i):
                     alive = ()

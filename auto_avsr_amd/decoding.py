@@ -320,6 +320,8 @@ class BatchBeamSearch(torch.nn.Module):
         if st is None:
             return None
         if k in self.part_scorers:
+            if hasattr(self.part_scorers[k], "keep_states"):  # (a partial scorer with a state of its own shape: ngram.NgramScorer)
+                return self.part_scorers[k].keep_states(st, keep)
             r, s = st
             return r[:, :, keep].contiguous(), s[keep]
         return [c[keep] for c in st]

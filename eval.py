@@ -50,6 +50,10 @@ def parse_args(argv=None):
                    help="contextual biasing: a file with one expected phrase per line -- a line of integers is token ids, any other line "
                         "is text (tokenised with the SentencePiece model); a boosted token must still be among the decoder's pre-beam candidates")
     p.add_argument("--bias-weight", type=float, default=0.0, help="reward per matched token of a bias phrase, in log units (0: no biasing)")
+    p.add_argument("--ngram-path", type=str, default=None, metavar="PATH",
+                   help="n-gram shallow fusion: a back-off n-gram language model as an ARPA text file over the token list's pieces (or over "
+                        "token ids, if every word is an integer); it scores the decoder's pre-beam candidates")
+    p.add_argument("--ngram-weight", type=float, default=0.0, help="weight of the n-gram model's log-probabilities (0: not used)")
     p.add_argument("--decode-mode", choices=["search", "rescore"], default="search",
                    help="search: the reference's label-synchronous hybrid CTC / attention beam search (default).  rescore: two-pass "
                         "decoding -- a CTC prefix beam search on the device, then one teacher-forced decoder (+ LM) pass over its n-best")
@@ -69,6 +73,8 @@ def parse_args(argv=None):
         p.error("--decode-batch groups the steps of the label-synchronous search: it does not apply to --decode-mode rescore")
     if (args.bias_list or args.bias_weight) and args.decode_mode == "rescore":
         p.error("--bias-list / --bias-weight bias the label-synchronous search: they do not apply to --decode-mode rescore")
+    if (args.ngram_path or args.ngram_weight) and args.decode_mode == "rescore":
+        p.error("--ngram-path / --ngram-weight fuse the model into the label-synchronous search: they do not apply to --decode-mode rescore")
     return args
 
 

@@ -615,6 +615,36 @@ int avsr_bias_score(const int32_t* first, const int32_t* tok, const int32_t* chi
  * session that never saw this call.  All utterances of a group share the list. */
 int avsr_beam_set_bias(int64_t handle, const int32_t* cfg, const float* fcfg, const int32_t* first, const int32_t* tok,
                        const int32_t* child, const int32_t* unc);
+/* Back-off n-gram language model (ARPA; shallow fusion, scorers["ngram"] / weights["ngram"]) as a PARTIAL scorer of the search: it
+ * scores the pre-beam candidates and <eos>.  Device tables that outlive their use: a node is a context (an n-gram of order < N, node 0
+ * the empty one); first int32 [n_nodes + 1] (node s owns the edges [first[s], first[s + 1])), tok int32 [n_edges] ascending within a
+ * node, logp f32 [n_edges] natural-log probabilities, next int32 [n_edges] = node of the longest suffix of (context + token), cut to
+ * N - 1 tokens, that is a node, bow f32 [n_nodes] back-off weights, back int32 [n_nodes] = node of the longest proper suffix of the
+ * context that is a node (0 if none).  log p(v | node s): walk s, back[s], ... to the first node with an edge e on v; logp[e] if that
+ * is s itself, otherwise r = bow[s0]; r += bow[s1]; ...; r += logp[e] in f32 and this order; the node reached is next[e]; the blank
+ * scores 0 and keeps the node.  The library checks the table SIZES, the start node's range and a finite weight only: the caller is
+ * responsible for the contents (first[] as for the bias tables, every next / back < n_nodes, back[] leading to node 0 within
+ * AVSR_NGRAM_MAX_ORDER hops -- the walk is cut there --, an edge on every token of the vocabulary but the blank at node 0).
+ * auto_avsr_amd/ngram.py (NgramScorer) builds them and is the one producer in this repository.  Bounds: */
+#define AVSR_NGRAM_MAX_NODES (1 << 26)
+#define AVSR_NGRAM_MAX_EDGES (1 << 27)
+#define AVSR_NGRAM_MAX_ORDER 16
+/* the lookup on its own: row r stands at node[r]; entry (r, c) of score / next [n][S + 1] = log-probability and node reached on
+ * cand[r][c] (c < S) or on eos (c = S).  n_nodes == 0 or n_edges == 0: zeros. */
+int avsr_ngram_score(const int32_t* first, const int32_t* tok, const float* logp, const int32_t* next_tab, const float* bow,
+                     const int32_t* back, int n_nodes, int n_edges, const int32_t* node, const int64_t* cand, int n, int S, int eos,
+                     int blank, float* score, int32_t* next, avsr_stream_t stream);
+/* bind a model to a session, replace it or (n_nodes == 0 or n_edges == 0) remove it, on the terms of avsr_beam_set_bias.  cfg:
+ * n_nodes, n_edges, start_node (the node of <s>, where every hypothesis starts); fcfg: weight.  With a model every step adds weight
+ * * log p after the CTC term at the entries it scores, carries node and running f32 sum per hypothesis (they follow the bias node and
+ * sum through update, keep and begin) and keeps the sums of the step's records for avsr_beam_ngram_sums; no launch is added, the
+ * lookups run inside the selection.  The host records stay [K][8].  The workspace grows by seven [rows] tables; without a model
+ * launches, workspace sizes and results are those of a session that never saw this call.  All utterances of a group share the model. */
+int avsr_beam_set_ngram(int64_t handle, const int32_t* cfg, const float* fcfg, const int32_t* first, const int32_t* tok, const float* logp,
+                        const int32_t* next_tab, const float* bow, const int32_t* back);
+/* the n-gram running sums of the records the last avsr_beam_step / avsr_beam_step_batch returned, in their packed order: out [*n_out]
+ * (at most U * beam floats); a host copy made inside the step's own synchronisation, no device work.  *n_out = 0 without a model. */
+int avsr_beam_ngram_sums(int64_t handle, float* out, int* n_out);
 /* the linear layer of a decoding step on its own: C = act(LN?(A) W^T + bias) + resid for M <= 128 rows (transformer_decoder.py:84-126
  * on one position per hypothesis); st_in [M][st_in_nt][2] per-row (sum, sum of squares) partials of A when ln_g != NULL;
  * st_out [M][ceil(N/16)][2] (may be NULL) the same for the rows of C, partial count per row through st_out_nt; partial: scratch of

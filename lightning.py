@@ -304,6 +304,14 @@ class ModelModule(_Base):
         bias = self._bias_scorer()
         if bias is not None:  # (either decoder takes it; eval.py's parse_args still refuses the flags with --decode-mode rescore)
             kw = dict(bias_phrases=bias, bias_weight=float(args.bias_weight))
+        ngram_path, ngram_weight = getattr(args, "ngram_path", None), float(getattr(args, "ngram_weight", 0.0) or 0.0)
+        if ngram_path or ngram_weight != 0.0:  # eval.py --ngram-path / --ngram-weight: the ARPA file is read once
+            cached = getattr(self, "_ngram", None)
+            if ngram_path and ngram_weight != 0.0 and (cached is None or cached[0] != ngram_path):
+                from auto_avsr_amd.ngram import NgramScorer
+
+                cached = self._ngram = (ngram_path, NgramScorer.from_arpa(ngram_path, self.token_list))
+            kw.update(ngram=cached[1] if (cached and cached[0] == ngram_path and ngram_weight != 0.0) else ngram_path, ngram_weight=ngram_weight)
         if not lm_path or lm_weight == 0.0:
             return make(self.model, self.token_list, **kw)
         cached = getattr(self, "_lm", None)
@@ -430,8 +438,34 @@ def _resolve_bias(token_list, bias_phrases, bias_weight, what="search"):
     return bias
 
 
+def _resolve_ngram(token_list, ngram, ngram_weight, what="search"):
+    """The `ngram` slot of get_beam_search_decoder: None, or an NgramScorer over the token list's vocabulary (given, or read from the
+    ARPA file at that path)."""
+    sc = None
+    if ngram is not None and ngram_weight != 0.0:
+        from auto_avsr_amd.ngram import NgramScorer
+
+        if isinstance(ngram, NgramScorer):
+            sc = ngram
+        elif isinstance(ngram, (str, bytes)) or hasattr(ngram, "__fspath__"):
+            sc = NgramScorer.from_arpa(ngram, token_list)
+        else:
+            raise TypeError("ngram: an NgramScorer or the path of an ARPA file")
+        if sc.n_vocab != len(token_list):
+            raise ValueError(f"the n-gram model's vocabulary ({sc.n_vocab}) is not the token list's ({len(token_list)})")
+    elif ngram_weight != 0.0:
+        import warnings
+
+        warnings.warn(f"ngram_weight={ngram_weight} without an n-gram model (ngram is None): the {what} runs without it")
+    elif ngram is not None:
+        import warnings
+
+        warnings.warn("ngram given without an n-gram weight (ngram_weight is 0): the model is not used")
+    return sc
+
+
 def get_two_pass_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight=0.1, lm_weight=0.0, beam_size=16,
-                         topk=16, nbest=None, bias_phrases=None, bias_weight=0.0):
+                         topk=16, nbest=None, bias_phrases=None, bias_weight=0.0, ngram=None, ngram_weight=0.0):
     """Not in the reference: the scorers and weights of get_beam_search_decoder behind auto_avsr_amd.two_pass.TwoPassDecoder -- a
     CTC prefix beam search on the device (beam_size entries, topk tokens per frame) whose nbest (default: all beam_size) are
     rescored by one teacher-forced decoder (+ language model) pass under the same objective.  bias_phrases / bias_weight as in
@@ -440,6 +474,9 @@ def get_two_pass_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty
     from auto_avsr_amd.two_pass import TwoPassDecoder
     from espnet.nets.scorers.length_bonus import LengthBonus
 
+    if ngram is not None or ngram_weight != 0.0:
+        raise NotImplementedError("two-pass decoding takes no n-gram model: neither the CTC prefix beam search of the first pass nor the "
+                                  "rescoring objective has the term; use get_beam_search_decoder(ngram=..., ngram_weight=...)")
     lm = _resolve_lm(model, token_list, rnnlm, rnnlm_conf, lm_weight, what="rescoring")
     bias = _resolve_bias(token_list, bias_phrases, bias_weight, what="rescoring")
     sos = eos = model.odim - 1
@@ -454,7 +491,7 @@ def get_two_pass_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty
 
 
 def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight=0.1, lm_weight=0.0,
-                            beam_size=40, bias_phrases=None, bias_weight=0.0):
+                            beam_size=40, bias_phrases=None, bias_weight=0.0, ngram=None, ngram_weight=0.0):
     """lightning.py:126-158: decoder (1 - ctc_weight) + CTC prefix scorer (ctc_weight) + length bonus (penalty), beam 40,
     pre-beam on the decoder scores.  No language model is shipped with the reference (`scorers["lm"] = None`); its `lm` slot is
     served here: rnnlm = an auto_avsr_amd.lm.TransformerLM, or the path of its state dict (ESPnet layout, optionally under a
@@ -462,7 +499,10 @@ def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, pena
     lm_weight = its weight in the score (shallow fusion).  lm_weight == 0 or rnnlm None: the search without a language model.
     Contextual biasing (not in the reference): bias_phrases = a list of phrases as token-id lists (or a ContextBiasScorer) puts an
     auto_avsr_amd.bias.ContextBiasScorer into a `bias` slot after `lm`, bias_weight = its weight in log units per matched token.  A
-    boosted token still has to be among the decoder's pre-beam candidates.  bias_weight == 0 or bias_phrases None: no biasing."""
+    boosted token still has to be among the decoder's pre-beam candidates.  bias_weight == 0 or bias_phrases None: no biasing.
+    N-gram shallow fusion (ESPnet's scorers["ngram"] / ngram_weight): ngram = an auto_avsr_amd.ngram.NgramScorer or the path of an ARPA
+    file over the token list's pieces (or token ids) puts a back-off n-gram model into an `ngram` slot after `ctc`: a partial scorer,
+    it scores the pre-beam candidates.  ngram_weight == 0 or ngram None: the search without it."""
     from espnet.nets.batch_beam_search import BatchBeamSearch
     from espnet.nets.scorers.length_bonus import LengthBonus
 
@@ -490,5 +530,9 @@ def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, pena
     scorers["length_bonus"] = LengthBonus(len(token_list))
     weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight, "bias": bias_weight if bias is not None else 0.0,
                "length_bonus": penalty}
+    ng = _resolve_ngram(token_list, ngram, ngram_weight)
+    if ng is not None:  # (after `ctc`: the partial scorers enter the score in their listed order)
+        scorers["ngram"] = ng
+        weights["ngram"] = ngram_weight
     return BatchBeamSearch(beam_size=beam_size, vocab_size=len(token_list), weights=weights, scorers=scorers, sos=sos, eos=eos,
                            token_list=token_list, pre_beam_score_key=None if ctc_weight == 1.0 else "decoder")

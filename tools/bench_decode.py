@@ -45,6 +45,10 @@ def main():
                          "(precise mode; python tools/bench_decode.py --bias > profiles/context_bias_decode.json).  With --two-pass: two-pass "
                          "decoding without and with the same list, alternated -- first pass and whole decode "
                          "(python tools/bench_decode.py --two-pass --bias > profiles/two_pass_bias_decode.json)")
+    ap.add_argument("--ngram", action="store_true",
+                    help="n-gram shallow-fusion rows instead of the default ones: a random 3-gram back-off model of about 10^6 n-grams, weight "
+                         "0.3 -- the native step without and with it, and the python-issued step with it, sides alternated "
+                         "(precise mode; python tools/bench_decode.py --ngram > profiles/ngram_decode.json)")
     ap.add_argument("--encode", action="store_true",
                     help="encoder-only rows instead of the default ones: 16 utterances around T = 100 and around T = 400 frames (lengths spread "
                          "+-20 %) through ModelModule.encode_many one at a time and in zero-padded groups of 4, 8 and 16, alternated, precise "
@@ -67,6 +71,8 @@ def main():
         return main_two_pass_bias(args)
     if args.bias:
         return main_bias(args)
+    if args.ngram:
+        return main_ngram(args)
     if args.two_pass or args.two_pass_once:
         return main_two_pass(args)
     import lightning
@@ -626,6 +632,100 @@ def main_bias(args):
                                 "1 000 random 2 - 5-token phrases (plus a few cut out of the unbiased winner), and the python-issued step with it; video "
                                 "E2E 250M decoder, search only (encoder output ready), wall clock between synchronisations, one warm-up then "
                                 "the sides alternated",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def main_ngram(args):
+    import random
+    import statistics
+
+    import lightning
+    from synth import synth_batch, synth_state_dict
+
+    from auto_avsr_amd import decoding
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+    from auto_avsr_amd.ngram import NgramScorer
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode.py --ngram needs an MI355X: there is nothing to time without one")
+    dev = torch.device("cuda:0")
+    V = 5049
+    m = E2E(V, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    toks = [str(i) for i in range(V)]
+    w_ngram = 0.3
+    AF.set_mode("precise")
+    rows = []
+    for T in (100, 400):
+        x, _, _ = synth_batch("video", 1, T, 3, V, seed=T, lengths=[T])
+        with torch.no_grad():
+            enc = m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float()
+        plain = lightning.get_beam_search_decoder(m, toks, beam_size=args.beam)
+        decoding.NATIVE_BEAM = True
+        with torch.no_grad():
+            first = plain(enc)[0].asdict()["yseq"][1:-1]
+        # a random 3-gram model of about 10^6 n-grams; random contexts never meet a hypothesis, so the winner's own n-grams are part of
+        # it: the search then stands at bigram contexts and backs off from them (the rest is the model's bulk)
+        rng = random.Random(11)
+        P = {(t,): -rng.uniform(2.0, 9.0) for t in range(1, V)}
+        P[(V,)] = -99.0
+        B = {(V,): -0.5}
+        seq = [V] + first + [V - 1]
+        bis = {tuple(seq[i: i + 2]) for i in range(len(seq) - 1)}
+        while len(bis) < 330000:
+            bis.add((rng.randint(1, V - 2), rng.randint(1, V - 1)))
+        bis = sorted(bis)
+        inner = [g for g in bis if g[1] != V - 1]
+        tris = {tuple(seq[i: i + 3]) for i in range(len(seq) - 2)}
+        while len(tris) < 665000:
+            tris.add(rng.choice(inner) + (rng.randint(1, V - 1),))
+        for g in bis:
+            P[g] = -rng.uniform(0.1, 6.0)
+            B.setdefault((g[0],), -rng.uniform(0.05, 2.0))
+        for g in tris:
+            P[g] = -rng.uniform(0.1, 5.0)
+            B.setdefault(g[:2], -rng.uniform(0.05, 2.0))
+        sc = NgramScorer(V, P, B, order=3)
+        mk = lambda: lightning.get_beam_search_decoder(m, toks, beam_size=args.beam, ngram=sc, ngram_weight=w_ngram)  # noqa: E731
+        sides = {"native_no_model": (plain, True), "native_ngram": (mk(), True), "python_ngram": (mk(), False)}
+        times, out = {k: [] for k in sides}, {}
+        for rep_ in range(args.reps + 1):  # first repetition = warm-up; the sides alternate within a repetition
+            for k, (bs, native) in sides.items():
+                decoding.NATIVE_BEAM = native
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                with torch.no_grad():
+                    out[k] = bs(enc)
+                torch.cuda.synchronize()
+                if rep_:
+                    times[k].append((time.perf_counter() - t0) * 1e3)
+                assert bool(bs._native) == native
+        row = {"T_frames": T, "beam": args.beam, "mode": "precise", "vocabulary": V, "ngram_weight": w_ngram, "order": sc.order,
+               "ngrams": len(P), "nodes": sc.n_nodes, "edges": sc.n_edges, "lookup_placement": "inside the selection block",
+               "repetitions": args.reps, "sides": {}}
+        for k in sides:
+            steps = max(len(h.asdict()["yseq"]) for h in out[k]) - 1
+            med = statistics.median(times[k])
+            row["sides"][k] = {"beam_search_ms": {"median": round(med, 2), "min": round(min(times[k]), 2), "max": round(max(times[k]), 2)},
+                               "longest_hypothesis_tokens": steps, "ms_per_token": round(med / max(steps, 1), 4),
+                               "best_ngram_sum": out[k][0].asdict()["scores"].get("ngram")}
+        a, b = row["sides"]["native_no_model"]["ms_per_token"], row["sides"]["native_ngram"]["ms_per_token"]
+        row["model_cost_ms_per_token"] = round(b - a, 4)
+        row["model_cost_relative"] = round(b / a - 1.0, 4)
+        row["native_and_python_step_agree_on_best"] = out["native_ngram"][0].asdict()["yseq"] == out["python_ngram"][0].asdict()["yseq"]
+        row["native_and_python_ngram_sums_bit_equal"] = (out["native_ngram"][0].asdict()["scores"]["ngram"]
+                                                         == out["python_ngram"][0].asdict()["scores"]["ngram"])
+        row["model_changes_best"] = out["native_ngram"][0].asdict()["yseq"] != out["native_no_model"][0].asdict()["yseq"]
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    AF.set_mode("bf16")
+    decoding.NATIVE_BEAM = True
+    print(json.dumps({"metric": "n-gram shallow fusion in the hybrid CTC / attention beam search: native one-call step without and with a random "
+                                "3-gram back-off model of about 10^6 n-grams (plus the n-grams of the model-free winner), and the python-issued "
+                                "step with it; video E2E 250M decoder, search only (encoder output ready), wall clock between synchronisations, "
+                                "one warm-up then the sides alternated",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
 
 
