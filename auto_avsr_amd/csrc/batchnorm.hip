@@ -273,6 +273,50 @@ __global__ __launch_bounds__(BN_THREADS) void bn_act_fwd_kernel(const T* __restr
     }
 }
 
+// bn_act_fwd_kernel (plain output forms) on a zero-padded batch [N][W][C] whose item n has min(W, max(0, lens[n]) * per) valid
+// rows: valid rows get the parent's expression (same operation order, same store rounding), every other row is written as
+// zeros -- a select, so nothing of a padded row of x / add reaches an output.  The audio front-end's 1-D trunk convolves
+// across time after every BatchNorm; with its BatchNorm + activation outputs zeroed beyond each utterance's own rows, those
+// rows are every following convolution's own zero padding.  grid = (vector chunks of one item, N): a block's first row decides
+// (block-uniform) whether it is all padding -- then it stores its zeros and returns before reading x.
+template <class T>
+__global__ __launch_bounds__(BN_THREADS) void bn_act_lens_fwd_kernel(const T* __restrict__ x, const T* __restrict__ add,
+                                                                     const float* __restrict__ mean,
+                                                                     const float* __restrict__ invstd,
+                                                                     const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta,
+                                                                     const int* __restrict__ lens, T* __restrict__ y, int W,
+                                                                     int C, int per, int act) {
+    const int cv = C >> 3;
+    const long nvec = (long)W * cv;  // vectors of one item
+    const long n = blockIdx.y;
+    const long valid = lens ? min((long)W, (long)max(lens[n], 0) * per) : (long)W;  // rows
+    const long v0 = (long)blockIdx.x * BN_THREADS;
+    const long i = v0 + threadIdx.x;
+    const long base = (n * nvec + i) * 8;
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) o[e] = 0.f;
+    if (v0 / cv >= valid) {  // (block-uniform) every row of this block lies beyond the length
+        if (i < nvec) store8(y + base, o);
+        return;
+    }
+    if (i >= nvec) return;
+    if (i / cv < valid) {
+        const int c = (int)(i % cv) * 8;
+        float v[8], mu[8], is[8], ga[8], be[8], ad[8];
+        load8(x + base, v);
+        load8(mean + c, mu);
+        load8(invstd + c, is);
+        load8(gamma + c, ga);
+        load8(beta + c, be);
+        if (add) load8(add + base, ad);
+#pragma unroll
+        for (int e = 0; e < 8; e++) o[e] = act_fwd((v[e] - mu[e]) * is[e] * ga[e] + be[e] + (add ? ad[e] : 0.f), act);
+    }
+    store8(y + base, o);
+}
+
 // The 3x3 / stride 2 / pad 1 case (the video stem) of bn_act_pool_fwd_kernel below, straight-line: all nine window loads
 // are issued up front from clamped addresses (out-of-image taps are masked afterwards), so a thread has 9 x 16 B in flight
 // instead of one load per loop trip.  (A 2 x 2-windows-per-thread variant -- 25 taps for four outputs -- was measured 2.5x
@@ -981,6 +1025,31 @@ extern "C" int avsr_bn_act_fwd(const void* x, const void* add, int dtype, const 
         AVSR_LAUNCH((bn_act_fwd_kernel<bf16_t>), grid, block, 0, stream, (const bf16_t*)x, (const bf16_t*)add, mean,
                     invstd, gamma, beta, (bf16_t*)y, (long)rows, C, act);
     AVSR_CHECK_LAUNCH("bn_act_fwd");
+    return 0;
+}
+
+// Evaluation of a zero-padded batch: x / add (may be NULL) / y [N][W][C] of one dtype (0 f32, 1 bf16, 2 f16); item n keeps
+// min(W, max(0, lens[n]) * per) rows, the others are written as zeros.  lens: int32 [N] on the device, NULL = every row valid.
+extern "C" int avsr_bn_act_lens_fwd(const void* x, const void* add, int dtype, const float* mean, const float* invstd,
+                                    const float* gamma, const float* beta, const int* lens, void* y, int N, int W, int C, int per,
+                                    int act, hipStream_t stream) {
+    AVSR_REQUIRE(C % 8 == 0, "batchnorm: C must be a multiple of 8");
+    AVSR_REQUIRE(dtype >= 0 && dtype <= 2, "bn_act_lens_fwd: dtype 0 (f32), 1 (bf16) or 2 (f16)");
+    AVSR_REQUIRE(per >= 1, "bn_act_lens_fwd: per (rows per frame) must be positive");
+    AVSR_REQUIRE(N <= 65535, "bn_act_lens_fwd: at most 65535 items");
+    if (N <= 0 || W <= 0) return 0;
+    const long nvec = (long)W * (C >> 3);
+    dim3 grid((unsigned)((nvec + BN_THREADS - 1) / BN_THREADS), N), block(BN_THREADS);
+    if (dtype == 0)
+        AVSR_LAUNCH((bn_act_lens_fwd_kernel<float>), grid, block, 0, stream, (const float*)x, (const float*)add, mean, invstd,
+                    gamma, beta, lens, (float*)y, W, C, per, act);
+    else if (dtype == 1)
+        AVSR_LAUNCH((bn_act_lens_fwd_kernel<bf16_t>), grid, block, 0, stream, (const bf16_t*)x, (const bf16_t*)add, mean,
+                    invstd, gamma, beta, lens, (bf16_t*)y, W, C, per, act);
+    else
+        AVSR_LAUNCH((bn_act_lens_fwd_kernel<f16_t>), grid, block, 0, stream, (const f16_t*)x, (const f16_t*)add, mean, invstd,
+                    gamma, beta, lens, (f16_t*)y, W, C, per, act);
+    AVSR_CHECK_LAUNCH("bn_act_lens_fwd");
     return 0;
 }
 

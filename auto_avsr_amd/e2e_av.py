@@ -50,14 +50,25 @@ class E2EAV(nn.Module):
         self.ctc = nets.CTC(odim, adim, 0.1, reduce=True)
         self.criterion = nets.LabelSmoothingLoss(odim, ignore_id, 0.1, False)
 
-    def encode(self, video, audio, lengths):
-        """video (B, T, 1, 88, 88), audio (B, 640 T, 1), lengths in video frames -> fused memory (B, T, D), mask."""
+    modality = "audiovisual"
+
+    def scorers(self):
+        """The scorers of hybrid CTC / attention beam search over the fused memory (as E2E.scorers)."""
+        from .decoding import CTCPrefixScorer
+
+        return dict(decoder=self.decoder, ctc=CTCPrefixScorer(self.ctc, self.eos))
+
+    def encode(self, video, audio, lengths=None):
+        """video (B, T, 1, 88, 88), audio (B, 640 T, 1), lengths in video frames -> fused memory (B, T, D), mask.
+        lengths None (evaluation of one unpadded utterance, or of equal-length ones): no mask, as the B = 1 decoding path of E2E."""
         vf = self.frontend(video)
         af = self.aux_frontend(audio)
         T = min(vf.shape[1], af.shape[1])  # 640 samples per frame: equal up to the last partial frame
         vf, af = vf[:, :T], af[:, :T]
-        lengths = lengths.to(vf.device)
-        mask = nets.non_pad_mask_device(lengths, T)
+        mask = None
+        if lengths is not None:
+            lengths = lengths.to(vf.device)
+            mask = nets.non_pad_mask_device(lengths, T)
         v, _ = self.encoder(AF.linear(vf, self.proj_encoder.weight, self.proj_encoder.bias, out_dtype=torch.float32), mask)
         a, _ = self.aux_encoder(AF.linear(af, self.aux_proj_encoder.weight, self.aux_proj_encoder.bias,
                                           out_dtype=torch.float32), mask)
@@ -72,6 +83,10 @@ class E2EAV(nn.Module):
         loss_att = self.criterion(pred, ys_out)
         loss = self.ctc_weight * loss_ctc + (1 - self.ctc_weight) * loss_att
         return loss, loss_ctc, loss_att, self.criterion.last_hits, n_tok[0]
+
+    def forward_pair(self, x, lengths, label):
+        """forward_tensors with E2E's three-argument signature, x = (video, audio): what the native training loop calls."""
+        return self.forward_tensors(x[0], x[1], lengths, label)
 
     def forward(self, video, audio, lengths, label):
         loss, loss_ctc, loss_att, hits, n_tok = self.forward_tensors(video, audio, lengths, label)

@@ -1446,4 +1446,4 @@ from .functional_heads import (  # noqa: E402,F401
     ScaleDropoutFn, scale_dropout, EmbedFn, embed, CtcLossFn, ctc_loss, ctc_align, ctc_beam_search, ctc_score, CeSmoothFn,
     ce_smooth, AddRowsFn, add, log_softmax)
 from .functional_frontend import (  # noqa: E402,F401
-    _bn_fwd_params, _bn_bwd, bn_tuple, BasicBlockFn, basic_block, StemFn, stem, AvgPoolFn, avg_pool)
+    _bn_fwd_params, _bn_bwd, bn_tuple, BasicBlockFn, basic_block, StemFn, stem, AvgPoolFn, avg_pool, trunk_1d)

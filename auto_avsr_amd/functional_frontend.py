@@ -1,6 +1,7 @@
 """Autograd glue of the front-ends (split out of functional.py in round 4): BasicBlockFn (ResNet block), StemFn (Conv3d /
 Conv1d stem + BatchNorm + SiLU (+ max-pool)), AvgPoolFn.  Re-exported by functional.py."""
 
+import contextlib
 import os
 
 import torch
@@ -38,6 +39,32 @@ def _conv_bn_stats(x, wp, Cin, Cout, KH, KW, rows, training):
     if not (training and _FUSE_BN_STATS and _state["mixed"] and ops.conv2d_takes_stats(x, wp, Cin, KH, KW, _state["precise"])):
         return None
     return torch.empty(ops.bn_stat_tiles(rows), 2, Cout, dtype=torch.float32, device=x.device)
+
+
+@contextlib.contextmanager
+def trunk_1d(frames):
+    """Entered by the audio front-end's 1-D trunk around its stem and blocks: `frames` is the batch's frame count Tmax (640 samples
+    each).  Inside AF.padded_lengths the trunk's BatchNorm + activation passes then zero every row beyond each utterance's own
+    length (_trunk1d_lens); outside that context nothing reads it.  The video trunk never enters: its frames are independent
+    images, and it keeps its launches under padded_lengths too."""
+    old = _state.get("trunk1d_frames")
+    _state["trunk1d_frames"] = int(frames)
+    try:
+        yield
+    finally:
+        _state["trunk1d_frames"] = old
+
+
+def _trunk1d_lens(x, N, W_out, training):
+    """Evaluation of a zero-padded batch (AF.padded_lengths) in the 1-D trunk: (lens, rows per frame at a layer whose output has
+    W_out rows per item); None everywhere else -- training, B = 1 decoding, the video trunk, audio-only evaluation."""
+    frames = _state.get("trunk1d_frames")
+    if frames is None or _state.get("pad_lens") is None:
+        return None
+    assert not training, "padded_lengths: evaluation only (the audio front-end is in training mode)"
+    assert not torch.is_grad_enabled(), "padded_lengths: no autograd through the length-exact path (use torch.no_grad())"
+    assert frames > 0 and W_out % frames == 0, f"padded_lengths: {W_out} rows per item do not divide into {frames} frames"
+    return AF._padded_lens_for(x, N), W_out // frames
 
 
 def _bn_bwd(c, dy, add, mean, invstd, bn, counts, rows, C, act, want_dadd, training):
@@ -96,6 +123,9 @@ class BasicBlockFn(torch.autograd.Function):
         # travel in the split8 layout -- written that way by the BatchNorm + activation pass, staged by the convolution without its
         # in-LDS conversion pass (csrc/gemm_split.hip, ACV = 2: stage-1 convolution 392 -> 294 us, tools/microbench_presplit.py).
         ps = _presplit_ok()
+        ml = _trunk1d_lens(x, N, OH * OW, training)  # 1-D trunk on a zero-padded batch: (lens, rows per frame); else None
+        if ml is not None:
+            ps = False  # (the masked pass writes the plain layouts only)
         if isinstance(x, ops.Split8) and not (pr and isinstance(wp1, ops.Split8) and (wd is None or isinstance(wpd, ops.Split8))):
             x = ops.scale_dropout(x, torch.float32)  # (a consumer that cannot read the layout: one pass back to plain f32)
         st1 = _conv_bn_stats(x, wp1, Cin, Cout, KH, KW, rows, training)
@@ -114,7 +144,10 @@ class BasicBlockFn(torch.autograd.Function):
         else:
             m1, i1, n1 = _bn_fwd_params(c1, rows, Cout, bn1, training, parts=st1)
         wp2 = _w_conv_fwd(w2, c1)
-        a1 = ops.bn_act_fwd(c1, None, m1, i1, g1, b1, rows, Cout, 1, out_split8=ps and isinstance(wp2, ops.Split8))
+        if ml is not None:
+            a1 = ops.bn_act_lens_fwd(c1, None, m1, i1, g1, b1, ml[0], ml[1], N, OH * OW, Cout, 1)
+        else:
+            a1 = ops.bn_act_fwd(c1, None, m1, i1, g1, b1, rows, Cout, 1, out_split8=ps and isinstance(wp2, ops.Split8))
         st2 = _conv_bn_stats(a1, wp2, Cout, Cout, KH, KW, rows, training)
         c2 = ops.conv2d_fwd(a1, wp2, N, OH, OW, Cout, Cout, KH, KW, 1, ph, pw, pr, stats=st2, wp_planes=wpl)
         m2, i2, n2 = _bn_fwd_params(c2, rows, Cout, bn2, training, parts=st2)
@@ -127,7 +160,11 @@ class BasicBlockFn(torch.autograd.Function):
             r = ops.bn_act_fwd(cd, None, md, idd, gd, bd, rows, Cout, 0)
         else:
             r = x
-        out = ops.bn_act_fwd(c2, r, m2, i2, g2, b2, rows, Cout, 1, out_split8=ps and Cout % 64 == 0)
+        if ml is not None:
+            # (the shortcut's BatchNorm above needs no mask: this pass zeroes the padded rows of the sum)
+            out = ops.bn_act_lens_fwd(c2, r, m2, i2, g2, b2, ml[0], ml[1], N, OH * OW, Cout, 1).view(c2.shape)
+        else:
+            out = ops.bn_act_fwd(c2, r, m2, i2, g2, b2, rows, Cout, 1, out_split8=ps and Cout % 64 == 0)
         sx = x_arg if (_state["hpf"] and x_arg.dtype == torch.bfloat16 and x_arg is not x) else _A(x)  # (the handed-over twin itself)
         ctx.save_for_backward(sx, _A(c1), _A(a1), _A(c2), _A(cd), _A(r) if wd is not None else None, w1, w2, wd, g1, b1, g2, b2,
                               gd, bd, m1, i1, n1, m2, i2, n2, md, idd, nd)
@@ -228,7 +265,11 @@ class StemFn(torch.autograd.Function):
             a0 = ops.bn_act_fwd(c0, None, m0, i0, g, b, rows, Cout, 1)
             out, idx = ops.maxpool2d_fwd(a0, B * Tn, OH, OW, Cout, 3, 2, 1)
         else:
-            out = ops.bn_act_fwd(c0, None, m0, i0, g, b, rows, Cout, 1)
+            ml = _trunk1d_lens(c0, B * Tn, OH * OW, training)  # the audio stem on a zero-padded batch: (lens, rows per frame)
+            if ml is not None:
+                out = ops.bn_act_lens_fwd(c0, None, m0, i0, g, b, ml[0], ml[1], B * Tn, OH * OW, Cout, 1)
+            else:
+                out = ops.bn_act_fwd(c0, None, m0, i0, g, b, rows, Cout, 1)
         ctx.save_for_backward(x, _A(c0), idx, g, b, m0, i0, n0, _A(xsel))
         ctx.meta = (geom, pool, training, bn_rest, (OH, OW), w.shape, geom_ok and not _bwd_precise())
         if _state["hpf"] and out.dtype == torch.float32 and _twin_of(out) is None and _state.get("tag_ok", True):

@@ -37,7 +37,8 @@ def capture_token():
 class StepGraphs:
     def __init__(self, eager_step, *, enabled=True, capture_after=1, max_graphs=64, thread_local=False, warm=None, on_fail=None,
                  evict=False, on_evict=None):
-        """eager_step(x, lens, y) -> tuple of device tensors: the WHOLE step.  It must START by dropping the parameters' gradient
+        """eager_step(x, lens, y) -> tuple of device tensors: the WHOLE step (x: a tensor, or a tuple of tensors -- the
+        audio-visual step's (video, audio) -- whose shapes and dtypes all enter the shape key).  It must START by dropping the parameters' gradient
         tensors (`p.grad = None`): the gradients a replay leaves behind live in the graph's memory pool, and an eager step (or a
         later capture) that found them would accumulate into them.  capture_after: eager visits of a shape before it is captured
         (0 = capture on first sight after a warm-up run of `warm(x, lens, y)` on a side stream -- what a benchmark wants).
@@ -66,10 +67,13 @@ class StepGraphs:
 
     @staticmethod
     def key(x, lens, y):
+        if isinstance(x, (tuple, list)):  # several input tensors (audio-visual: (video, audio)): keyed element-wise
+            return (tuple(tuple(t.shape) for t in x), tuple(lens.shape), tuple(y.shape), tuple(t.dtype for t in x), y.dtype)
         return (tuple(x.shape), tuple(lens.shape), tuple(y.shape), x.dtype, y.dtype)
 
     def _capture(self, key, x, lens, y):
-        sx, sl, sy = x.clone(), lens.clone(), y.clone()
+        sx = tuple(t.clone() for t in x) if isinstance(x, (tuple, list)) else x.clone()
+        sl, sy = lens.clone(), y.clone()
         if self.warm is not None:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -131,7 +135,11 @@ class StepGraphs:
         else:
             self.graphs.move_to_end(key)
             g, sx, sl, sy, outs = ent
-            sx.copy_(x, non_blocking=True)
+            if isinstance(sx, tuple):  # (copied element-wise into the graph's static buffers)
+                for st, t in zip(sx, x):
+                    st.copy_(t, non_blocking=True)
+            else:
+                sx.copy_(x, non_blocking=True)
             sl.copy_(lens, non_blocking=True)
             sy.copy_(y, non_blocking=True)
         g.replay()

@@ -508,6 +508,22 @@ def bn_act_fwd(x, add, mean, invstd, gamma, beta, rows, C, act, out_split8=False
     return y
 
 
+def bn_act_lens_fwd(x, add, mean, invstd, gamma, beta, lens, per, N, W, C, act):
+    """bn_act_fwd on a zero-padded batch x [N, W, C] (evaluation, functional.padded_lengths): item n keeps its first
+    min(W, max(0, lens[n]) * per) rows, every other row of the result is zero.  lens: int32 [N] on x's device, in encoder frames
+    (None = every row is valid); per: rows per frame at this layer.  Plain output in x's dtype (f32 / f16 / bf16): no twin, no
+    split8 layout."""
+    assert not isinstance(x, Split8) and not isinstance(add, Split8), "bn_act_lens_fwd: plain layouts only"
+    assert x.is_contiguous() and x.numel() == N * W * C, (tuple(x.shape), N, W, C)
+    assert add is None or (add.dtype == x.dtype and add.is_contiguous() and add.numel() == x.numel())
+    if lens is not None:
+        assert lens.dtype == torch.int32 and lens.numel() == N and lens.is_contiguous() and lens.device == x.device
+    y = torch.empty_like(x)
+    call("avsr_bn_act_lens_fwd", _ptr(x), _ptr(add), dt(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(lens), _ptr(y),
+         N, W, C, per, act, _stream(x), nbytes=_nb(x, add, y))
+    return y
+
+
 def bn_act_pool_fwd(x, mean, invstd, gamma, beta, N, H, W, C, K, S, P, act, want_xsel=False, out_split8=False):
     """maxpool(act(bn(x))) without the full-resolution activation; returns (y, idx) like maxpool2d_fwd -- and with
     want_xsel (3x3 / stride 2 / pad 1 only) also xsel, the raw x at every arg-max."""

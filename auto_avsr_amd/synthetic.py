@@ -36,7 +36,7 @@ def bucket_batches(lengths, max_frames=1600, num_buckets=400):
 
 
 def make_batch(lengths, idxs, modality="video", odim=5049, seed=0, device="cpu", on_device=False):
-    """One collated batch: inputs (B,T,1,88,88) [audio: (B,640T,1)] zero-padded, input_lengths (B,),
+    """One collated batch: inputs (B,T,1,88,88) [audio: (B,640T,1); audiovisual: the pair of both, lengths in frames] zero-padded, input_lengths (B,),
     targets (B,1,L) padded with -1; L_i = max(1, round(T_i/6.5)) ids uniform in [1, odim-2].
     on_device: draw the input samples with the DEVICE's generator (a training loop that makes a fresh batch per step cannot wait
     80 ms for 12 M host-side normal deviates + a 50 MB upload in front of a 22 ms step); labels / lengths as always."""
@@ -50,17 +50,20 @@ def make_batch(lengths, idxs, modality="video", odim=5049, seed=0, device="cpu",
     y = torch.full((B, 1, L), -1, dtype=torch.int64)
     for b, n in enumerate(ls):
         y[b, 0, :n] = torch.randint(1, odim - 1, (n,), generator=g)
-    if modality == "video":
+    if modality in ("video", "audiovisual"):
         x = torch.zeros(B, T, 1, 88, 88)
         for b, t in enumerate(ts):
             x[b, :t] = torch.randn(t, 1, 88, 88, generator=g)
         lens = torch.tensor(ts, dtype=torch.int64)
-    else:
-        x = torch.zeros(B, T * 640, 1)
+    if modality != "video":
+        xa = torch.zeros(B, T * 640, 1)
         for b, t in enumerate(ts):
             w = torch.randn(t * 640, generator=g)
-            x[b, : t * 640, 0] = (w - w.mean()) / w.std()
-        lens = torch.tensor(ts, dtype=torch.int64) * 640
+            xa[b, : t * 640, 0] = (w - w.mean()) / w.std()
+    if modality == "audiovisual":  # both inputs, the video's lengths (frames) and labels
+        return (x.to(device), xa.to(device)), lens.to(device), y.to(device), sum(ts)
+    if modality != "video":
+        x, lens = xa, torch.tensor(ts, dtype=torch.int64) * 640
     return x.to(device), lens.to(device), y.to(device), sum(ts)
 
 
@@ -73,19 +76,22 @@ def _make_batch_on_device(lengths, idxs, modality, odim, seed, dev, g):
     for b, n in enumerate(ls):
         y[b, 0, :n] = torch.randint(1, odim - 1, (n,), generator=g)
     tl = torch.tensor(ts, dtype=torch.int64)
-    if modality == "video":
+    if modality in ("video", "audiovisual"):
         x = torch.randn(B, T, 1, 88, 88, device=dev, generator=gd)
         x *= (torch.arange(T, device=dev)[None, :] < tl.to(dev)[:, None]).view(B, T, 1, 1, 1)  # zero padding
         lens = tl
-    else:
-        x = torch.randn(B, T * 640, device=dev, generator=gd)
+    if modality != "video":
+        xa = torch.randn(B, T * 640, device=dev, generator=gd)
         valid = torch.arange(T * 640, device=dev)[None, :] < (tl.to(dev) * 640)[:, None]
-        x = x * valid
+        xa = xa * valid
         n = (tl.to(dev) * 640).float()[:, None]
-        mean = x.sum(1, keepdim=True) / n
-        var = (((x - mean) * valid) ** 2).sum(1, keepdim=True) / (n - 1)
-        x = (((x - mean) / var.sqrt()) * valid).unsqueeze(-1)
-        lens = tl * 640
+        mean = xa.sum(1, keepdim=True) / n
+        var = (((xa - mean) * valid) ** 2).sum(1, keepdim=True) / (n - 1)
+        xa = (((xa - mean) / var.sqrt()) * valid).unsqueeze(-1)
+    if modality == "audiovisual":
+        return (x, xa), lens.to(dev), y.to(dev), sum(ts)
+    if modality != "video":
+        x, lens = xa, tl * 640
     return x, lens.to(dev), y.to(dev), sum(ts)
 
 

@@ -15,6 +15,14 @@ import torch
 import torch.distributed as dist
 
 
+def _forward_tensors(model, x, lens, y):
+    """model.forward_tensors on a batch of the loop: x is one tensor, or the (video, audio) pair of the audio-visual model
+    (E2EAV.forward_pair)."""
+    if isinstance(x, (tuple, list)):
+        return model.forward_pair(x, lens, y)
+    return model.forward_tensors(x, lens, y)
+
+
 class _Hot(torch.nn.Module):
     """forward_tensors() behind nn.Module.__call__ so that DDP's reducer hooks see the step."""
 
@@ -23,7 +31,7 @@ class _Hot(torch.nn.Module):
         self.m = m
 
     def forward(self, x, lens, y):
-        return self.m.forward_tensors(x, lens, y)
+        return _forward_tensors(self.m, x, lens, y)
 
 
 def save_checkpoint(folder, epoch, model, opt, global_step, keep=10, opt_state=None):
@@ -69,9 +77,9 @@ def validate(model, batches, world):
     over batches and ranks."""
     was_training = model.training
     model.eval()
-    tot = torch.zeros(5, device=batches[0][0].device) if batches else None
+    tot = torch.zeros(5, device=batches[0][1].device) if batches else None
     for x, lens, y, _ in batches:
-        loss, loss_ctc, loss_att, hits, ntok = model.forward_tensors(x, lens, y)
+        loss, loss_ctc, loss_att, hits, ntok = _forward_tensors(model, x, lens, y)
         tot += torch.stack([loss, loss_ctc, loss_att, hits / ntok.clamp_min(1), torch.ones_like(loss)])
     model.train(was_training)
     if tot is None:
@@ -127,7 +135,8 @@ class _FileSource:
 
     def _triples(self, loader):
         for b in loader:
-            yield b["inputs"].to(self.dev), b["input_lengths"].to(self.dev), b["targets"].to(self.dev)
+            x = (b["videos"].to(self.dev), b["audios"].to(self.dev)) if "videos" in b else b["inputs"].to(self.dev)
+            yield x, b["input_lengths"].to(self.dev), b["targets"].to(self.dev)
 
     def epoch(self, epoch, global_step):
         self.dm._train_loaders = epoch - 1  # (DataModule._train_epoch: the loader handed out next serves this epoch)
@@ -258,6 +267,7 @@ class NativeStepper:
                                         total_steps=int(args.max_epochs * steps_per_epoch), cast_weights=dev.type == "cuda",
                                         graph_shapes=_max_graphs())
         params = list(model.parameters())
+        warmed = []  # (non-empty once the weight-copy tables were built outside a capture, see full_step)
 
         def full_step(x, lens, y):
             """ONE training step, start to end, with no host decision that depends on the batch's values: what runs eagerly the
@@ -272,7 +282,7 @@ class NativeStepper:
             AF.refresh_weight_cache()  # conv-weight permutes; the Linear copies were rewritten by the optimizer step itself
             loss, loss_ctc, loss_att, hits, ntok = hot(x, lens, y)
             if world > 1:
-                bs = torch.full((1,), float(x.shape[0]), device=dev)
+                bs = torch.full((1,), float(y.shape[0]), device=dev)
                 allb = torch.empty(world, device=dev)
                 if buckets is not None and buckets.comm is not None:
                     AF._state["bn_comm"].all_gather(allb, bs)
@@ -283,6 +293,13 @@ class NativeStepper:
             if buckets is not None:
                 buckets.finish()
             opt.step()
+            if not warmed and not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+                # once, after the first eager step: the weight-copy tables are rebuilt (a host-to-device copy, illegal under capture)
+                # by the first refresh that finds the copies this step created -- that must not be the refresh of a capture, which
+                # it would be when the very next step repeats this step's shape (a single-shape corpus, a repeated batch).  The
+                # refresh rewrites the copies from the weights as they are now; the next step's own refresh writes the same values.
+                AF.refresh_weight_cache()
+                warmed.append(True)
             if buckets is not None and not buckets.rebuilt and not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
                 for p in params:  # (after the first step: buckets in the order the gradients arrived -- ddp.GradBuckets.rebuild_by_arrival)
                     p.grad = None

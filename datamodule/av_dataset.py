@@ -1,5 +1,5 @@
 """Utterance datasets behind the reference's `AVDataset` contract (datamodule/av_dataset.py:29-73): item =
-{"input": transformed clip, "target": token ids}; `input_lengths` (frames) drives the length bucketing.
+{"input": transformed clip, "target": token ids} -- audiovisual: {"video", "audio", "target"}; `input_lengths` (frames) drives the length bucketing.
 
 * `AVDataset` reads the reference's on-disk layout -- `<root>/<dataset>/<rel_path>` mp4 (96x96 RGB, 25 fps) + the wav next
   to it, listed by a CSV of `dataset,rel_path,frames,token ids`.  Decoding needs torchvision (mp4) -- absent from this
@@ -41,6 +41,13 @@ def load_audio(path):
         return torch.from_numpy(pcm.astype(np.float32) / 32768.0)[:, :1]
 
 
+def cut_or_pad(audio, size):
+    """Waveform (S, 1) cut or zero-padded to `size` samples (640 per video frame: both streams then have the same frame count)."""
+    if audio.shape[0] >= size:
+        return audio[:size]
+    return torch.nn.functional.pad(audio, (0, 0, 0, size - audio.shape[0]))
+
+
 class AVDataset(torch.utils.data.Dataset):
     """Items are RAW: {"input": decoded clip [T, 3, H, W] uint8 / waveform [T, 1] f32 on the HOST, "target": token ids}.
     The reference applies `video_transform` / `audio_transform` here, on the CPU, inside DataLoader workers; this build's
@@ -71,6 +78,9 @@ class AVDataset(torch.utils.data.Dataset):
         path = os.path.join(self.root_dir, dataset_name, rel_path)
         if self.modality == "video":
             return {"input": load_video(path), "target": token_id}
+        if self.modality == "audiovisual":  # (the key names of upstream's audio-visual release)
+            video = load_video(path)
+            return {"video": video, "audio": cut_or_pad(load_audio(path), self.rate_ratio * len(video)), "target": token_id}
         return {"input": load_audio(path), "target": token_id}
 
     def __len__(self):
@@ -79,7 +89,7 @@ class AVDataset(torch.utils.data.Dataset):
 
 class SyntheticAVDataset(torch.utils.data.Dataset):
     """`n` synthetic utterances in the form the model consumes AFTER the reference's transforms: video (T, 1, 88, 88)
-    z-normalised noise, audio (640 T, 1) layer-normed noise; targets round(T / 6.5) ids uniform in [1, odim - 2]."""
+    z-normalised noise, audio (640 T, 1) layer-normed noise, audiovisual {"video", "audio"} with both; targets round(T / 6.5) ids uniform in [1, odim - 2]."""
 
     def __init__(self, n, modality="video", odim=5049, seed=0, lengths=None, device="cpu"):
         from auto_avsr_amd.synthetic import utterance_lengths
@@ -91,12 +101,14 @@ class SyntheticAVDataset(torch.utils.data.Dataset):
         g = torch.Generator().manual_seed(7919 * self.seed + idx)
         t = self.input_lengths[idx]
         target = torch.randint(1, self.odim - 1, (max(1, int(round(t / 6.5))),), generator=g)
-        if self.modality == "video":
+        if self.modality in ("video", "audiovisual"):
             x = torch.randn(t, 1, 88, 88, generator=g)
-        else:
+        if self.modality != "video":
             w = torch.randn(t * 640, generator=g)
-            x = ((w - w.mean()) / w.std()).unsqueeze(1)
-        return {"input": x.to(self.device), "target": target.to(self.device)}
+            a = ((w - w.mean()) / w.std()).unsqueeze(1)
+        if self.modality == "audiovisual":  # both streams, each from the generator of its single modality, in that order
+            return {"video": x.to(self.device), "audio": a.to(self.device), "target": target.to(self.device)}
+        return {"input": (x if self.modality == "video" else a).to(self.device), "target": target.to(self.device)}
 
     def __len__(self):
         return len(self.input_lengths)

@@ -53,11 +53,12 @@ class DeviceBatches:
     def sampler(self):  # (what a trainer looks at to find a DistributedSampler)
         return getattr(self.loader, "sampler", None)
 
-    def _inputs(self, raws):
+    def _inputs(self, raws, stream=None):
+        """stream: "video" / "audio" of an audiovisual dataset (both transforms are configured; noise goes to the audio only)."""
         from auto_avsr_amd import transforms as TR
 
         xs = [r.to(self.device, non_blocking=True) for r in raws]
-        if self.ds.modality == "video":
+        if (stream or self.ds.modality) == "video":
             return TR.video_batch(xs, self.ds.video_transform.subset)
         at = self.ds.audio_transform
         return TR.audio_batch(xs, at.subset, at.add_noise)
@@ -75,6 +76,16 @@ class DeviceBatches:
             self._seen = getattr(smp, "epoch", None)
         self.epoch += 1
         for item in self.loader:
+            if self.ds.modality == "audiovisual":
+                items = [item] if self.single else item
+                v, lens = self._inputs([s["video"] for s in items], "video")
+                a, _ = self._inputs([s["audio"] for s in items], "audio")
+                if self.single:
+                    yield {"video": v[0], "audio": a[0], "target": item["target"].to(self.device)}
+                    continue
+                t, tl = pad([s["target"].to(self.device) for s in item], -1)
+                yield {"videos": v, "audios": a, "input_lengths": torch.tensor(lens), "targets": t, "target_lengths": torch.tensor(tl)}
+                continue
             if self.single:
                 x, _ = self._inputs([item["input"]])
                 yield {"input": x[0], "target": item["target"].to(self.device)}
@@ -131,13 +142,14 @@ class DataModule(_DMBase):
         # only the transform of the selected modality is built (the audio one loads the babble recording, which is data and
         # not part of this repository); at test time noise is added only for a real target SNR (999999 = the reference's "clean")
         at = vt = None
-        if self.args.modality == "video":
+        if self.args.modality in ("video", "audiovisual"):
             vt = VideoTransform(subset)
-        elif subset == "test":
-            snr = getattr(self.args, "decode_snr_target", 999999)
-            at = AudioTransform("test", snr_target=snr if snr is not None and snr < 999999 else None)
-        else:
-            at = AudioTransform(subset)
+        if self.args.modality in ("audio", "audiovisual"):  # (audiovisual: noise goes to the audio stream only)
+            if subset == "test":
+                snr = getattr(self.args, "decode_snr_target", 999999)
+                at = AudioTransform("test", snr_target=snr if snr is not None and snr < 999999 else None)
+            else:
+                at = AudioTransform(subset)
         return AVDataset(root_dir=self.args.root_dir, label_path=os.path.join(self.args.root_dir, "labels", label_file),
                          subset=subset, modality=self.args.modality, audio_transform=at, video_transform=vt)
 

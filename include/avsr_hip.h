@@ -216,6 +216,13 @@ int avsr_convmod_dwbn_bwd(const void* a, const void* c, const void* ds, int dtyp
 int avsr_bn_act_fwd(const void* x, const void* add, int dtype, const float* mean, const float* invstd,
                     const float* gamma, const float* beta, void* y, int64_t rows, int C, int act,
                     avsr_stream_t stream);
+/* Evaluation of a zero-padded batch, x / add (may be NULL) / y [N][W][C] of one dtype (0 f32, 1 bf16, 2 f16):
+ * y[n,w,:] = w < min(W, max(0, lens[n]) * per) ? act(gamma*(x-mean)*invstd + beta (+ add)) : 0 -- avsr_bn_act_fwd's expression
+ * on the valid rows, zeros (a select: NaN / Inf of a padded row reaches no output) on the others.  lens: int32 [N] on the
+ * device, in encoder frames; per: rows per frame at this layer; lens == NULL: every row is valid. */
+int avsr_bn_act_lens_fwd(const void* x, const void* add, int dtype, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, const int* lens, void* y, int N, int W, int C, int per,
+                         int act, avsr_stream_t stream);
 /* f32 in / f32 out + the bf16 twin y2 of the output.  layout (round 5): bit 0 -- y is written in the "split8" layout (every group
  * of 8 consecutive values as its 8 hi bf16 + 8 lo bf16: the bytes of the f32 tensor, and what avsr_conv2d_f32s* consumes as a
  * pre-split A operand -- tile codes 23 - 26 -- without a conversion pass); bit 1 -- `add` is stored in that layout */

@@ -28,8 +28,50 @@ def compute_word_level_distance(seq1, seq2):
     return prev[-1]
 
 
+def _load_checked(dst, sub, where):
+    """load_state_dict(sub) into dst, after naming the first key whose shape does not fit (torch's own message lists all of them
+    without saying which checkpoint they came from)."""
+    have = dst.state_dict()
+    for k, v in sub.items():
+        if k in have and tuple(have[k].shape) != tuple(v.shape):
+            raise ValueError(f"{where}: shape mismatch for {k!r}: the checkpoint has {tuple(v.shape)}, the model {tuple(have[k].shape)}")
+    dst.load_state_dict(sub)
+
+
+def load_pretrained_av(model, args):
+    """Audio-visual model (not in the reference): --pretrained-video-path / --pretrained-audio-path initialise the two stacks from
+    single-modality checkpoints -- `frontend` / `proj_encoder` / `encoder` go to the same names for video and to `aux_*` for audio.
+    The heads (`decoder`, `ctc`) come from the video checkpoint when there is one, else from the audio checkpoint; `fusion` keeps
+    its initialisation.  A shape mismatch is an error that names the key."""
+    heads_done = False
+    for flag, prefix in (("pretrained_video_path", ""), ("pretrained_audio_path", "aux_")):
+        path = getattr(args, flag, None)
+        if not path:
+            continue
+        ckpt = torch.load(path, map_location="cpu")
+        for part in ("frontend", "proj_encoder", "encoder"):
+            sub = {k[len(part) + 1:]: v for k, v in ckpt.items() if k.startswith(part + ".")}
+            _load_checked(getattr(model, prefix + part), sub, f"{path} -> {prefix + part}")
+        if not heads_done:
+            for part in ("decoder", "ctc"):
+                sub = {k[len(part) + 1:]: v for k, v in ckpt.items() if k.startswith(part + ".")}
+                if sub:
+                    _load_checked(getattr(model, part), sub, f"{path} -> {part}")
+                    heads_done = True
+
+
+def av_pair(sample):
+    """(video (T, 1, 88, 88), audio (640 T, 1)) of an audio-visual sample given as {"video", "audio", ...} or as a pair."""
+    if isinstance(sample, dict):
+        return sample["video"], sample["audio"]
+    video, audio = sample
+    return video, audio
+
+
 def load_pretrained(model, args):
     """Weight-transfer modes of lightning.py:30-46 (front-end only / front-end + proj + encoder / full model)."""
+    if getattr(args, "modality", None) == "audiovisual":
+        load_pretrained_av(model, args)
     path = getattr(args, "pretrained_model_path", None)
     if not path:
         return
@@ -65,7 +107,12 @@ class ModelModule(_Base):
         self.modality = args.modality
         self.text_transform = TextTransform()
         self.token_list = self.text_transform.token_list
-        self.model = E2E(len(self.token_list), self.modality, ctc_weight=getattr(args, "ctc_weight", 0.1))
+        if self.modality == "audiovisual":  # (not in the reference snapshot: auto_avsr_amd/e2e_av.py)
+            from auto_avsr_amd.e2e_av import E2EAV
+
+            self.model = E2EAV(len(self.token_list), ctc_weight=getattr(args, "ctc_weight", 0.1))
+        else:
+            self.model = E2E(len(self.token_list), self.modality, ctc_weight=getattr(args, "ctc_weight", 0.1))
         load_pretrained(self.model, args)
         # train.py --trainer-step native: Lightning's MANUAL optimisation -- training_step runs the whole step itself (forward,
         # backward, data-parallel exchange, fused clip + AdamW + schedule) through auto_avsr_amd.train_native.NativeStepper, i.e.
@@ -133,9 +180,12 @@ class ModelModule(_Base):
 
     # ---- the hot path (lightning.py:86-114)
     def _step(self, batch, batch_idx, step_type):
-        loss, loss_ctc, loss_att, acc = self.model(batch["inputs"], batch["input_lengths"], batch["targets"])
+        if self._is_av():
+            loss, loss_ctc, loss_att, acc = self.model(batch["videos"], batch["audios"], batch["input_lengths"], batch["targets"])
+        else:
+            loss, loss_ctc, loss_att, acc = self.model(batch["inputs"], batch["input_lengths"], batch["targets"])
         if HAVE_LIGHTNING:
-            bs = len(batch["inputs"])
+            bs = len(batch["targets"])
             sfx = "" if step_type == "train" else "_val"
             self.log("loss" + sfx, loss, on_step=step_type == "train", on_epoch=True, batch_size=bs,
                      sync_dist=step_type != "train")
@@ -159,9 +209,10 @@ class ModelModule(_Base):
                 self._native_opt_state = sd
 
     def _native_training_step(self, batch):
-        loss, loss_ctc, loss_att, hits, ntok = self._native(batch["inputs"], batch["input_lengths"], batch["targets"])
+        x = (batch["videos"], batch["audios"]) if self._is_av() else batch["inputs"]
+        loss, loss_ctc, loss_att, hits, ntok = self._native(x, batch["input_lengths"], batch["targets"])
         if HAVE_LIGHTNING:
-            bs = len(batch["inputs"])
+            bs = len(batch["targets"])
             self.log("loss", loss, on_step=True, on_epoch=True, batch_size=bs)
             self.log("loss_ctc", loss_ctc, on_step=False, on_epoch=True, batch_size=bs, sync_dist=True)
             self.log("loss_att", loss_att, on_step=False, on_epoch=True, batch_size=bs, sync_dist=True)
@@ -177,7 +228,7 @@ class ModelModule(_Base):
         AF.new_step()  # per-step registries of the kernels' autograd glue (zero-scratch arena, twin / hand-over tables)
         loss = self._step(batch, batch_idx, "train")
         if HAVE_LIGHTNING:
-            sizes = self.all_gather(batch["inputs"].size(0))
+            sizes = self.all_gather(batch["targets"].size(0))
             loss = loss * (sizes.size(0) / sizes.sum())  # world size / total batch size (lightning.py:88-90)
         return loss
 
@@ -185,12 +236,25 @@ class ModelModule(_Base):
         return self._step(batch, batch_idx, "val")
 
     # ---- evaluation (lightning.py:54-84,116-123): beam search over the encoder output
-    def _decode(self, sample):
-        """Front-end -> encoder (no mask, B = 1) -> hybrid CTC/attention beam search -> text (lightning.py:54-64)."""
+    def _is_av(self):
+        """Audio-visual model?  (getattr: tests and tools assemble a ModelModule without __init__ and may leave `modality` unset)"""
+        return getattr(self, "modality", None) == "audiovisual"
+
+    def _encode_one(self, sample):
+        """Front-end -> encoder of ONE unpadded utterance (no mask, B = 1) -> (T, D).  Audio-visual: `sample` is {"video", "audio"} or
+        a (video, audio) pair, and the result is the fused memory of both stacks (E2EAV.encode)."""
+        if self._is_av():
+            video, audio = av_pair(sample)
+            mem, _ = self.model.encode(video.unsqueeze(0), audio.unsqueeze(0), None)
+            return mem.squeeze(0)
         x = self.model.frontend(sample.unsqueeze(0))
         x = self.model.proj_encoder(x)
         enc_feat, _ = self.model.encoder(x, None)
-        enc_feat = enc_feat.squeeze(0)
+        return enc_feat.squeeze(0)
+
+    def _decode(self, sample):
+        """Front-end -> encoder (no mask, B = 1) -> hybrid CTC/attention beam search -> text (lightning.py:54-64)."""
+        enc_feat = self._encode_one(sample)
         nbest_hyps = self.beam_search(enc_feat)
         nbest_hyps = [h.asdict() for h in nbest_hyps[: min(len(nbest_hyps), 1)]]
         predicted_token_id = torch.tensor(list(map(int, nbest_hyps[0]["yseq"][1:])))
@@ -214,9 +278,7 @@ class ModelModule(_Base):
 
     def align(self, sample, token_ids):
         """Word timestamps ({"word", "start", "end"} in seconds, 40 ms per encoder frame) of a given transcript of `sample`."""
-        x = self.model.proj_encoder(self.model.frontend(sample.unsqueeze(0)))
-        enc_feat, _ = self.model.encoder(x, None)
-        return self.align_encoded(enc_feat.squeeze(0), token_ids)[0]
+        return self.align_encoded(self._encode_one(sample), token_ids)[0]
 
     def _timestamp_record(self, enc_feat, token_ids, text):
         words, score = self.align_encoded(enc_feat, token_ids)
@@ -225,24 +287,24 @@ class ModelModule(_Base):
     def encode_many(self, samples, batch=0, max_frames=None):
         """Not in the reference: the encoder outputs (T_i, D) of several utterances, in the order of `samples`, each a contiguous
         tensor of its own.  batch <= 1: front-end / encoder one utterance at a time, unpadded, as in `_decode`.  batch > 1
-        (video only): utterances are sorted by length and taken greedily in groups of at most `batch` while B * Tmax stays within
+        (video and audiovisual -- grouped by video length, `samples` then being {"video", "audio"} dicts or (video, audio) pairs):
+        utterances are sorted by length and taken greedily in groups of at most `batch` while B * Tmax stays within
         `max_frames` (default: args.max_frames, else 1600, the training bound; an utterance longer than that forms a group of its
         own); a group is zero-padded to Tmax and runs front-end -> proj_encoder -> encoder ONCE, under the attention key mask and
         auto_avsr_amd.functional.padded_lengths -- the convolution modules then convolve over each utterance's own frames only,
         so every utterance is encoded as it is alone (the reference's masked padded forward is not: its depthwise convolution
         reads the padded frames, conformer_encoder.py:30-35)."""
         if batch <= 1:
-            encs = []
-            for sample in samples:
-                x = self.model.proj_encoder(self.model.frontend(sample.unsqueeze(0)))
-                enc_feat, _ = self.model.encoder(x, None)
-                encs.append(enc_feat.squeeze(0))
-            return encs
+            return [self._encode_one(sample) for sample in samples]
         if self.modality == "audio":
             raise NotImplementedError(
-                "encode_many(batch > 1) is video only: the audio front-end's 1-D ResNet trunk normalises and then convolves across "
-                "time in every block, so padded frames stop being zero after its first BatchNorm and the trunk would need each "
-                "utterance's length at every layer")
+                "encode_many(batch > 1) is refused for audio alone: the audio front-end's 1-D ResNet trunk is length-aware by now "
+                "(inside padded_lengths its BatchNorm + activation passes zero every row beyond the utterance's length, which is "
+                "what audiovisual grouping runs on), but the audio-only refusal is pinned by tests; lifting it is a follow-up")
+        av = self._is_av()
+        if av:
+            pairs = [av_pair(s) for s in samples]
+            samples, audios = [p[0] for p in pairs], [p[1] for p in pairs]
         from auto_avsr_amd import functional as AF
         from auto_avsr_amd.nets import non_pad_mask_device
 
@@ -266,6 +328,18 @@ class ModelModule(_Base):
                 for b, i in enumerate(g):
                     x[b, :lens[b]] = samples[i]
                 lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
+                if av:
+                    # both stacks and the fusion once per group: the audio is cut or zero-padded to 640 samples per video frame;
+                    # E2EAV.encode builds the one key mask both encoders share
+                    xa = audios[g[0]].new_zeros((len(g), 640 * tmax) + tuple(audios[g[0]].shape[1:]))
+                    for b, i in enumerate(g):
+                        n = min(640 * lens[b], audios[i].shape[0])
+                        xa[b, :n] = audios[i][:n]
+                    with AF.padded_lengths(lens_dev, self.model):
+                        enc, _ = self.model.encode(x, xa, lens_dev)
+                    for b, i in enumerate(g):
+                        encs[i] = enc[b, :lens[b]].clone()
+                    continue
                 mask = non_pad_mask_device(lens_dev, tmax)
                 with AF.padded_lengths(lens_dev, self.model):
                     h = self.model.proj_encoder(self.model.frontend(x))
@@ -368,7 +442,7 @@ class ModelModule(_Base):
         self.beam_search = self._make_beam_search()
 
     def test_step(self, sample, sample_idx):
-        predicted = self._decode(sample["input"])
+        predicted = self._decode(sample if self._is_av() else sample["input"])
         if getattr(self, "timestamp_records", None) is not None:  # eval.py --timestamps: align the hypothesis just decoded
             self.timestamp_records.append(self._timestamp_record(*self._last_decoded, predicted))
         actual = self.text_transform.post_process(sample["target"])

@@ -53,7 +53,10 @@ def main():
                     help="encoder-only rows instead of the default ones: 16 utterances around T = 100 and around T = 400 frames (lengths spread "
                          "+-20 %) through ModelModule.encode_many one at a time and in zero-padded groups of 4, 8 and 16, alternated, precise "
                          "and mixed modes, then a whole --decode-mode rescore decode without and with encode_batch 16 "
-                         "(python tools/bench_decode.py --encode > profiles/encode_batch.json)")
+                         "(python tools/bench_decode.py --encode > profiles/encode_batch.json).  With --modality audiovisual: the same for "
+                         "the audio-visual model (both front-ends, both encoders, the fusion head), groups of 4 and 8, whole decode with "
+                         "encode_batch 8 (python tools/bench_decode.py --encode --modality audiovisual > profiles/encode_batch_av.json)")
+    ap.add_argument("--modality", choices=["video", "audiovisual"], default="video", help="--encode: the model whose encoder side is timed")
     ap.add_argument("--bias-weight", type=float, default=1.0, help="--two-pass --bias: the weight of the list")
     ap.add_argument("--rescore-beam", type=int, default=16)
     ap.add_argument("--rescore-topk", type=int, default=16)
@@ -386,7 +389,13 @@ def main_encode(args):
     from auto_avsr_amd.e2e import E2E
 
     dev = torch.device("cuda:0")
-    m = E2E(5049, "video")
+    av = args.modality == "audiovisual"
+    if av:
+        from auto_avsr_amd.e2e_av import E2EAV
+
+        m = E2EAV(5049)
+    else:
+        m = E2E(5049, "video")
     m.load_state_dict(synth_state_dict(m.state_dict(), 3))
     m = m.to(dev).eval()
     toks = [str(i) for i in range(5049)]
@@ -399,7 +408,7 @@ def main_encode(args):
 
     mod = lightning.ModelModule.__new__(lightning.ModelModule)
     torch.nn.Module.__init__(mod)
-    mod.modality, mod.model, mod.text_transform, mod.token_list = "video", m, Text(), toks
+    mod.modality, mod.model, mod.text_transform, mod.token_list = args.modality, m, Text(), toks
     mod.args = argparse.Namespace(decode_mode="rescore", rescore_beam=args.rescore_beam, rescore_topk=args.rescore_topk)
     decoding.NATIVE_BEAM = True
     N = 16
@@ -408,7 +417,10 @@ def main_encode(args):
         g = torch.Generator().manual_seed(T)
         lens = [round(T * (0.8 + 0.4 * i / (N - 1))) for i in range(N)]  # T - 20 % .. T + 20 %
         lens = [lens[i] for i in torch.randperm(N, generator=g).tolist()]
-        return lens, [torch.randn(n, 1, 88, 88, generator=g).to(dev) for n in lens]
+        videos = [torch.randn(n, 1, 88, 88, generator=g).to(dev) for n in lens]
+        if not av:
+            return lens, videos
+        return lens, [(v, torch.randn(640 * n, 1, generator=g).to(dev)) for v, n in zip(videos, lens)]  # (unit-variance noise)
 
     def groups_of(lens, batch, max_frames=1600):  # the groups encode_many forms (sizes only)
         sizes, cur = [], 0
@@ -431,7 +443,8 @@ def main_encode(args):
         return (time.perf_counter() - t0) * 1e3, out
 
     rows = []
-    sides = (1, 4, 8, 16)
+    sides = (1, 4, 8) if av else (1, 4, 8, 16)
+    top = sides[-1]
     for mode in ("precise", "mixed"):
         AF.set_mode(mode)
         AF.invalidate_weight_cache()
@@ -467,15 +480,15 @@ def main_encode(args):
     mod.beam_search = mod._make_beam_search()
     for T in (100, 400):
         lens, samples = utterances(T)
-        ts, hyps = {0: [], 16: []}, {}
+        ts, hyps = {0: [], top: []}, {}
         for rep in range(args.reps + 1):
-            for eb in (0, 16):
+            for eb in (0, top):
                 t, out = timed(lambda: mod.decode_many(samples, workers=1, encode_batch=eb))
                 if rep:
                     ts[eb].append(t)
                 else:
                     hyps[eb] = out
-        for eb in (0, 16):
+        for eb in (0, top):
             rows.append({"what": "whole decode, --decode-mode rescore", "mode": "precise", "T_frames_nominal": T, "utterances": N,
                          "encode_batch": eb, "rescore_beam": args.rescore_beam, "rescore_topk": args.rescore_topk, "ms_for_all": stats(ts[eb]),
                          "utterances_per_sec_median": round(N / (statistics.median(ts[eb]) / 1e3), 2),
@@ -484,9 +497,12 @@ def main_encode(args):
             print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
         del samples
     AF.set_mode("bf16")
-    print(json.dumps({"metric": "encoder side of evaluation (front-end + proj_encoder + 12 Conformer layers) alone: one utterance at a time "
-                                "(B = 1, unpadded) against length-exact zero-padded groups (ModelModule.encode_many, max_frames 1600), video E2E "
-                                "250M; then the whole two-pass decode without and with encode_batch 16",
+    what = ("encoder side of evaluation (two front-ends + proj_encoders + 2 x 12 Conformer layers + fusion head)" if av else
+            "encoder side of evaluation (front-end + proj_encoder + 12 Conformer layers)")
+    print(json.dumps({"metric": what + " alone: one utterance at a time "
+                                "(B = 1, unpadded) against length-exact zero-padded groups (ModelModule.encode_many, max_frames 1600), "
+                                + ("audio-visual E2EAV" if av else "video E2E 250M") +
+                                f"; then the whole two-pass decode without and with encode_batch {top}",
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights; 16 utterances per row, lengths spread +-20 % around T",
                       "timing": f"wall time between device synchronisations; sides alternated inside each of {args.reps} repetitions after one "
                                 "warm-up repetition; median [min, max]",

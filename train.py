@@ -11,7 +11,7 @@ def parse_args(argv=None):
     p.add_argument("--exp-dir", default="./exp", type=str, help="directory for checkpoints and logs")
     p.add_argument("--exp-name", default="run", type=str)
     p.add_argument("--group-name", default=None, type=str)
-    p.add_argument("--modality", default="video", type=str, choices=["audio", "video"])
+    p.add_argument("--modality", default="video", type=str, choices=["audio", "video", "audiovisual"])
     p.add_argument("--root-dir", default=None, type=str)
     p.add_argument("--train-file", default=None, type=str)
     p.add_argument("--val-file", default="lrs3_test_transcript_lengths_seg16s.csv", type=str)
@@ -19,6 +19,10 @@ def parse_args(argv=None):
     p.add_argument("--num-nodes", default=4, type=int)
     p.add_argument("--gpus", default=8, type=int)
     p.add_argument("--pretrained-model-path", default=None, type=str)
+    p.add_argument("--pretrained-video-path", default=None, type=str,
+                   help="--modality audiovisual: a video checkpoint for the video stack (frontend / proj_encoder / encoder) and the heads")
+    p.add_argument("--pretrained-audio-path", default=None, type=str,
+                   help="--modality audiovisual: an audio checkpoint for the audio stack (aux_frontend / aux_proj_encoder / aux_encoder)")
     p.add_argument("--transfer-frontend", action="store_true")
     p.add_argument("--transfer-encoder", action="store_true")
     p.add_argument("--warmup-epochs", default=5, type=int)
