@@ -28,6 +28,15 @@
 //       of rule 2) depend on the frame's tokens only: ctc_root_child_kernel resolves them off the chain, one binary search per (b, t,
 //       k) among the root's children, and the search stages the result with the token rows.  Only an entry that stands at a
 //       non-root node reads the tables inside the frame loop (P1: its unc; P2: its own edges, for the live extensions).
+//   avsr_ctc_beam_search_ngram   the same search (plain or biased) with a back-off n-gram model (the tables and the lookup rule of
+//       auto_avsr_amd/ngram.py): ctc_beam_kernel<BIAS, true>.  Every beam entry also carries the model's node of its prefix and the
+//       running f32 sum G of its log-probabilities -- again functions of the tokens alone -- and P3 ranks by total (+ bias) + weight *
+//       G + len_bonus * length.  Every back-off walk ends at the root, whose edge on a token depends on the frame's tokens only:
+//       ctc_ngram_root_kernel resolves (logp, next) of the root per (b, t, k) off the chain and the search stages them with the token
+//       rows.  P2 walks the levels below the root for the live extensions of an entry that stands below it (binary search among the
+//       node's own edges, then back[]) and, without a bias list, keeps (G', next) of all W K extensions in LDS for the winners of P4
+//       (65 120 bytes of static LDS); with a list those two arrays would take the kernel to 76 640 bytes, so there the W winners redo
+//       their walk (60 256 bytes).  Keeping measured 15 - 17 % faster on the first pass than walking twice.
 //   avsr_ctc_score   N label sequences per utterance against one [T][V] matrix of log-posteriors: label builder of ctc_common.h
 //       per sequence, a gather of the 2L+1 extended-label columns, and the alpha recursion of the loss (one wave per sequence).
 #include "prims.h"
@@ -41,6 +50,8 @@ constexpr int CB_MAXC = CB_MAXW * (CB_MAXK + 1);  // candidates of a frame
 constexpr int CB_FCH = 8;                         // frames per staged chunk of (token, lp) rows
 constexpr int CB_STG = 3;                         // registers per thread that hold the next chunk: 8 * 65 words <= 3 * 256
 constexpr int CB_STG_BIAS = 4;                    // ... with the root children of the tokens: 8 * 97 words <= 4 * 256
+constexpr int CB_STG_NGRAM = 5;                   // ... with the root's (logp, next) on the tokens: 8 * 129 words <= 5 * 256
+constexpr int CB_STG_BIAS_NGRAM = 6;              // ... with both: 8 * 161 words <= 6 * 256
 constexpr int CB_NT_MIN = 256, CB_NT_MAX = 1024;  // threads of the search's block
 constexpr int TK_NT = 256;
 
@@ -160,6 +171,69 @@ __global__ __launch_bounds__(256) void ctc_root_child_kernel(const int32_t* __re
     rootc[i] = found;
 }
 
+// ---- n-gram model: per (utterance, frame, token slot) the root's log-probability of the token and the node reached
+struct NgramTabs {
+    const int32_t *first, *tok;
+    const float* logp;
+    const int32_t* next;
+    const float* bow;
+    const int32_t* back;
+};
+// edge of node s on token v, -1 if there is none (tok[] ascending within a node).  A plain binary search: one workgroup's scattered
+// loads are bounded by the number of load instructions rather than by their latency -- a search that narrows by 8 with 7 probes in
+// flight, and level headers requested a level ahead, measured 12 % slower on the first pass than this one.
+AVSR_DEV int ng_edge(const NgramTabs& g, int s, int v) {
+    int lo = g.first[s], hi = g.first[s + 1];
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1, x = g.tok[mid];
+        if (x == v) return mid;
+        if (x < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return -1;
+}
+// the root's edge on v: NgramScorer's root holds the tokens 1 .. V - 1 in order, so the edge is tried at its place first
+AVSR_DEV int ng_root_edge(const NgramTabs& g, int v) {
+    const int lo = g.first[0], hi = g.first[1], e = lo + v - 1;
+    if (e >= lo && e < hi && g.tok[e] == v) return e;
+    return ng_edge(g, 0, v);
+}
+// log p(v | node s) and the node reached, the f32 additions in the order of ngram.py: walk s, back[s], ... to the first node with an
+// edge e on v; logp[e] if that is s itself, else r = bow[s0]; r += bow[s1]; ...; r += logp[e].  (ur, un): the root's (logp, next) on
+// v, resolved by the caller, so the levels below the root are all this reads.  The walk is cut after AVSR_NGRAM_MAX_ORDER hops
+// (tables are not validated: a cycle in back[] must not hang the search).  Additions only: there is nothing to contract.
+AVSR_DEV float ng_lookup(const NgramTabs& g, int s, int v, float ur, int un, int& next) {
+    float r = 0.f;
+    bool fresh = true;
+    for (int hop = 0; s != 0 && hop < AVSR_NGRAM_MAX_ORDER; hop++) {
+        const int e = ng_edge(g, s, v);
+        if (e >= 0) {
+            next = g.next[e];
+            return fresh ? g.logp[e] : r + g.logp[e];
+        }
+        r = fresh ? g.bow[s] : r + g.bow[s];
+        fresh = false;
+        s = g.back[s];
+    }
+    if (s != 0) {
+        next = 0;
+        return r;
+    }
+    next = un;
+    return fresh ? ur : r + ur;
+}
+__global__ __launch_bounds__(256) void ctc_ngram_root_kernel(const int32_t* __restrict__ tok, const int64_t* __restrict__ in_lens,
+                                                             NgramTabs g, int K, int Tlen, long total, float* __restrict__ ulogp,
+                                                             int32_t* __restrict__ unext) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long row = i / K;
+    if ((int64_t)(row % Tlen) >= in_lens[row / Tlen]) return;  // (no token set was written for this frame)
+    const int e = ng_root_edge(g, tok[i]);
+    ulogp[i] = e >= 0 ? g.logp[e] : 0.f;  // (a root without the edge: the caller's tables are broken, the token scores 0)
+    unext[i] = e >= 0 ? g.next[e] : 0;
+}
+
 struct BeamArgs {
     const int32_t* tok;  // [B][T][K]
     const float* val;    // [B][T][K]
@@ -179,21 +253,34 @@ struct BeamArgsBias : BeamArgs {  // contextual biasing: what ctc_beam_kernel<tr
     float* bias_sum;     // [B][nbest]
     int32_t* bias_node;  // [B][nbest]
 };
-template <bool BIAS>
+struct BeamArgsNgram : BeamArgsBias {  // n-gram model: what ctc_beam_kernel<*, true> takes on top (the bias fields unused without a list)
+    const float* ulogp;    // [B][T][K]
+    const int32_t* unext;  // [B][T][K]
+    NgramTabs ng;
+    int ng_start, ng_eos;
+    float ng_weight, len_bonus;
+    float* ngram_sum;     // [B][nbest]
+    int32_t* ngram_node;  // [B][nbest]
+};
+template <bool BIAS, bool NGRAM>
 struct BeamArgsOf {
     typedef BeamArgs type;
 };
 template <>
-struct BeamArgsOf<true> {
+struct BeamArgsOf<true, false> {
     typedef BeamArgsBias type;
+};
+template <bool BIAS>
+struct BeamArgsOf<BIAS, true> {
+    typedef BeamArgsNgram type;
 };
 
 // a candidate's bias step in one word: the node reached (< 2^24 = AVSR_BIAS_MAX_NODES), +1 taken, unc of the parent's node taken back
 constexpr int CB_BIAS_PLUS = 1 << 24, CB_BIAS_BACK = 1 << 25, CB_BIAS_NODE = (1 << 24) - 1;
 
 // ---- one workgroup per utterance walks its frames
-template <bool BIAS>
-__global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf<BIAS>::type a) {
+template <bool BIAS, bool NGRAM>
+__global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf<BIAS, NGRAM>::type a) {
     // the beam, double buffered: hash of the prefix and of its parent prefix, last token, length, node id, pb, pnb, total
     __shared__ uint64_t s_h[2][CB_MAXW], s_hp[2][CB_MAXW];
     __shared__ int s_last[2][CB_MAXW], s_len[2][CB_MAXW], s_node[2][CB_MAXW];
@@ -205,14 +292,23 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
     __shared__ float s_cpnb[CB_MAXC], s_cpb[CB_MAXW];
     __shared__ int s_rank[CB_MAXC];  // candidates that beat candidate s, summed over the parts of the block
     __shared__ int s_live;           // candidates of the frame that carry mass
-    // per frame of a chunk: K tokens, K values, the blank's value (BIAS: and the K root children of the tokens)
-    __shared__ int s_stage[2][CB_FCH * ((BIAS ? 3 : 2) * CB_MAXK + 1)];
+    // per frame of a chunk: K tokens, K values, the blank's value (BIAS: and the K root children of the tokens; NGRAM: and the root's
+    // K log-probabilities and K next nodes on the tokens)
+    constexpr int ROWS = 2 + (BIAS ? 1 : 0) + (NGRAM ? 2 : 0);
+    __shared__ int s_stage[2][CB_FCH * (ROWS * CB_MAXK + 1)];
     // BIAS: trie node and sum of gains of the beam's entries, unc of the current entries' nodes, the candidates' packed steps
     __shared__ int s_bn[2][BIAS ? CB_MAXW : 1], s_bg[2][BIAS ? CB_MAXW : 1], s_bu[BIAS ? CB_MAXW : 1];
     __shared__ int s_cb[BIAS ? CB_MAXW * CB_MAXK : 1];
-    constexpr int STG = BIAS ? CB_STG_BIAS : CB_STG;
+    // NGRAM: the model's node and running sum G (f32 bits) of the beam's entries
+    __shared__ int s_nn[2][NGRAM ? CB_MAXW : 1], s_ng[2][NGRAM ? CB_MAXW : 1];
+    // ... and, where 64 KB of LDS hold them (without a bias list), G and node of every extension, so that the winners of P4 need not
+    // walk again (with a list they do: the same loads a moment later)
+    constexpr bool KEEP = NGRAM && !BIAS;
+    __shared__ int s_cr[KEEP ? CB_MAXW * CB_MAXK : 1], s_cx[KEEP ? CB_MAXW * CB_MAXK : 1];
+    constexpr int STG = NGRAM ? (BIAS ? CB_STG_BIAS_NGRAM : CB_STG_NGRAM) : (BIAS ? CB_STG_BIAS : CB_STG);
+    static_assert(CB_FCH * (ROWS * CB_MAXK + 1) <= STG * CB_NT_MIN, "the staged chunk must fit the registers that hold it");
     const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
-    const int W = a.W, K = a.K, T = a.T, K1 = K + 1, RW = (BIAS ? 3 : 2) * K + 1;
+    const int W = a.W, K = a.K, T = a.T, K1 = K + 1, RW = ROWS * K + 1;
     // P3: the block is `parts` groups of Cw threads (whole waves); group g compares every candidate with its share of the others
     const int Cw = (W * K1 + 63) / 64 * 64, parts = Cw <= NT ? NT / Cw : 1;
     const int part = parts > 1 ? tid / Cw : 0, s_first = parts > 1 ? tid - part * Cw : tid, s_step = parts > 1 ? Cw : NT;
@@ -226,8 +322,18 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
     int32_t* g_beam = a.beam + (long)b * T * W * 4;
     const int32_t* g_root = nullptr;
     if constexpr (BIAS) g_root = a.rootc + (long)b * T * K;
+    const float* g_ulogp = nullptr;
+    const int32_t* g_unext = nullptr;
+    if constexpr (NGRAM) {
+        g_ulogp = a.ulogp + (long)b * T * K;
+        g_unext = a.unext + (long)b * T * K;
+    }
 
     if (tid == 0) {
+        if constexpr (NGRAM) {
+            s_nn[0][0] = a.ng_start;
+            s_ng[0][0] = __builtin_bit_cast(int, 0.f);
+        }
         if constexpr (BIAS) {
             s_bn[0][0] = 0;
             s_bg[0][0] = 0;
@@ -258,8 +364,12 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
             if (f < CB_FCH && t < Tb) {
                 if (x < K) v = g_tok[(long)t * K + x];
                 else if (x < 2 * K) v = __builtin_bit_cast(int, g_val[(long)t * K + x - K]);
-                else if (!BIAS || x == 2 * K) v = __builtin_bit_cast(int, g_blk[t]);
-                else v = g_root[(long)t * K + x - 2 * K - 1];
+                else if ((!BIAS && !NGRAM) || x == 2 * K) v = __builtin_bit_cast(int, g_blk[t]);
+                else if (BIAS && (!NGRAM || x < 3 * K + 1)) v = g_root[(long)t * K + x - 2 * K - 1];
+                else if constexpr (NGRAM) {
+                    const int y = x - (BIAS ? 3 : 2) * K - 1;
+                    v = y < K ? __builtin_bit_cast(int, g_ulogp[(long)t * K + y]) : g_unext[(long)t * K + y - K];
+                }
             }
             pre[q] = v;
         }
@@ -283,6 +393,8 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
         const float* st_val = reinterpret_cast<const float*>(st_tok + K);
         const float lpb = st_val[K];
         const int* st_root = st_tok + 2 * K + 1;  // (BIAS only)
+        const int* st_unext = st_tok + (BIAS ? 3 : 2) * K + 1 + K;  // (NGRAM only: the root's next nodes, after its log-probabilities)
+        const float* st_ulogp = reinterpret_cast<const float*>(st_unext - K);
         const int n = s_n[cur], nxt = cur ^ 1, N = n * K1, stamp = t + 1;
         // ---- P1: parent slots, token slots of the last tokens, merged extensions
         for (int p = tid; p < n * n; p += NT) {
@@ -351,6 +463,20 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
                 }
                 v += a.b_weight * (float)g;
             }
+            if constexpr (NGRAM) {  // ... + weight * G(prefix) + len_bonus * len(prefix); only an extension below the root reads the tables
+                float G = __builtin_bit_cast(float, s_ng[cur][i]);
+                int len = s_len[cur][i];
+                if (k < K && v > neg_inf()) {
+                    int nx;
+                    G += ng_lookup(a.ng, s_nn[cur][i], st_tok[k], st_ulogp[k], st_unext[k], nx);
+                    len += 1;
+                    if constexpr (KEEP) {
+                        s_cr[i * K + k] = __builtin_bit_cast(int, G);
+                        s_cx[i * K + k] = nx;
+                    }
+                }
+                v += a.ng_weight * G + a.len_bonus * (float)len;
+            }
             s_cv[s] = v;
             s_rank[s] = 0;
             alive += v > neg_inf();
@@ -399,8 +525,18 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
             const int rank = s_rank[s], live = s_live;
             if (rank >= W) continue;
             const int i = s / K1, k = s - i * K1, r = rank;
-            if constexpr (BIAS) {  // the pure CTC total, as P2 computed it, and the bias state of the prefix
-                v = k == K ? lse2(s_cpb[i], s_cpnb[s]) : s_cpnb[s];
+            if constexpr (BIAS || NGRAM) v = k == K ? lse2(s_cpb[i], s_cpnb[s]) : s_cpnb[s];  // the pure CTC total, as P2 computed it
+            if constexpr (NGRAM) {  // the model's state of the prefix: a winner that is an extension reads what P2 kept, or walks once more
+                int nn = s_nn[cur][i];
+                float G = __builtin_bit_cast(float, s_ng[cur][i]);
+                if (k < K && KEEP) {
+                    G = __builtin_bit_cast(float, s_cr[i * K + k]);
+                    nn = s_cx[i * K + k];
+                } else if (k < K) G += ng_lookup(a.ng, nn, st_tok[k], st_ulogp[k], st_unext[k], nn);
+                s_nn[nxt][r] = nn;
+                s_ng[nxt][r] = __builtin_bit_cast(int, G);
+            }
+            if constexpr (BIAS) {  // the bias state of the prefix
                 const int step = k == K ? 0 : s_cb[i * K + k];
                 s_bn[nxt][r] = k == K ? s_bn[cur][i] : step & CB_BIAS_NODE;
                 s_bg[nxt][r] = s_bg[cur][i] + ((step & CB_BIAS_PLUS) != 0) - ((step & CB_BIAS_BACK) ? s_bu[i] : 0);
@@ -477,6 +613,17 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
         if constexpr (BIAS) {  // <eos> is never in the trie: it takes the uncommitted part back
             a.bias_sum[(long)b * nbest + r] = ok ? (float)(s_bg[cur][r] - a.b_unc[s_bn[cur][r]]) : 0.f;
             a.bias_node[(long)b * nbest + r] = ok ? s_bn[cur][r] : 0;
+        }
+        if constexpr (NGRAM) {  // a finished hypothesis also pays for its </s>
+            float G = 0.f;
+            if (ok) {
+                const int e = ng_root_edge(a.ng, a.ng_eos);
+                int nx;
+                G = __builtin_bit_cast(float, s_ng[cur][r]);
+                G += ng_lookup(a.ng, s_nn[cur][r], a.ng_eos, e >= 0 ? a.ng.logp[e] : 0.f, e >= 0 ? a.ng.next[e] : 0, nx);
+            }
+            a.ngram_sum[(long)b * nbest + r] = G;
+            a.ngram_node[(long)b * nbest + r] = ok ? s_nn[cur][r] : 0;
         }
         if (ok) {
             int node = s_node[cur][r];
@@ -580,6 +727,14 @@ struct BiasList {  // what avsr_ctc_beam_search_bias adds to the plain call
     int32_t* node;
 };
 
+struct NgramModel {  // what avsr_ctc_beam_search_ngram adds to either
+    NgramTabs tabs;
+    int start, eos;
+    float weight, len_bonus;
+    float* sum;
+    int32_t* node;
+};
+
 __global__ __launch_bounds__(256) void ctc_bias_zero_kernel(float* __restrict__ bias_sum, int32_t* __restrict__ bias_node, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
@@ -601,10 +756,11 @@ extern "C" int64_t avsr_ctc_beam_workspace_bytes(int B, int T, int W, int K) {
     return beam_rec_offset(B, T, W, K) + (int64_t)B * T * W * 16;
 }
 
-// the plain search (bias == nullptr) or the search with a bias list, whose root-child table follows the plain layout
+// the plain search (bias == nullptr) or the search with a bias list, whose root-child table follows the plain layout; with an n-gram
+// model (ng != nullptr) the root's (logp, next) tables follow either
 static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest, int32_t* tokens,
                        int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid, void* workspace, int B, int T, int V,
-                       hipStream_t stream, const BiasList* bias) {
+                       hipStream_t stream, const BiasList* bias, const NgramModel* ng = nullptr) {
     AVSR_REQUIRE(W >= 2 && W <= CB_MAXW, "ctc_beam_search: beam must be 2 .. 64");
     AVSR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V - 1, "ctc_beam_search: token budget must be 1 .. min(32, V - 1)");
     AVSR_REQUIRE(nbest >= 1 && nbest <= W, "ctc_beam_search: nbest must be 1 .. beam");
@@ -613,7 +769,7 @@ static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int 
     AVSR_REQUIRE(T >= 1 && (int64_t)T * W < (1 << 30), "ctc_beam_search: 1 .. 2^30 / beam frames");
     AVSR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_beam_search: workspace must be 16-byte aligned");
     if (B <= 0) return 0;
-    BeamArgsBias a;
+    BeamArgsNgram a;
     int32_t* tok = reinterpret_cast<int32_t*>(workspace);
     float* val = reinterpret_cast<float*>(tok + (int64_t)B * T * K);
     float* blk = val + (int64_t)B * T * K;
@@ -639,8 +795,27 @@ static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int 
     // four threads per candidate where a block can hold them (the rank loop of P3 is the longest stretch of a frame), whole waves
     int nt = (W * (K + 1) + 63) / 64 * 64 * 4;
     nt = nt < CB_NT_MIN ? CB_NT_MIN : (nt > CB_NT_MAX ? CB_NT_MAX : nt);
+    const long total = (long)B * T * K;
+    if (ng != nullptr) {
+        char* after = reinterpret_cast<char*>(workspace) +
+                      (bias ? avsr_ctc_beam_bias_workspace_bytes(B, T, W, K) : avsr_ctc_beam_workspace_bytes(B, T, W, K));
+        float* ulogp = reinterpret_cast<float*>(after);
+        int32_t* unext = reinterpret_cast<int32_t*>(after + align16(total * 4));
+        a.ulogp = ulogp;
+        a.unext = unext;
+        a.ng = ng->tabs;
+        a.ng_start = ng->start;
+        a.ng_eos = ng->eos;
+        a.ng_weight = ng->weight;
+        a.len_bonus = ng->len_bonus;
+        a.ngram_sum = ng->sum;
+        a.ngram_node = ng->node;
+        AVSR_LAUNCH(ctc_ngram_root_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tok, in_lens, a.ng, K, T, total, ulogp,
+                    unext);
+    }
     if (bias == nullptr) {
-        AVSR_LAUNCH(ctc_beam_kernel<false>, dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgs&>(a));
+        if (ng == nullptr) AVSR_LAUNCH((ctc_beam_kernel<false, false>), dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgs&>(a));
+        else AVSR_LAUNCH((ctc_beam_kernel<false, true>), dim3(B), dim3(nt), 0, stream, a);
     } else {
         int32_t* rootc = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + avsr_ctc_beam_workspace_bytes(B, T, W, K));
         a.rootc = rootc;
@@ -651,10 +826,10 @@ static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int 
         a.b_weight = bias->weight;
         a.bias_sum = bias->sum;
         a.bias_node = bias->node;
-        const long total = (long)B * T * K;
         AVSR_LAUNCH(ctc_root_child_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tok, in_lens, a.b_first, a.b_tok,
                     a.b_child, K, T, total, rootc);
-        AVSR_LAUNCH(ctc_beam_kernel<true>, dim3(B), dim3(nt), 0, stream, a);
+        if (ng == nullptr) AVSR_LAUNCH((ctc_beam_kernel<true, false>), dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgsBias&>(a));
+        else AVSR_LAUNCH((ctc_beam_kernel<true, true>), dim3(B), dim3(nt), 0, stream, a);
     }
     AVSR_CHECK_LAUNCH("ctc_beam_search");
     return 0;
@@ -689,6 +864,49 @@ extern "C" int avsr_ctc_beam_search_bias(const float* lp, int64_t ld, const int6
     }
     const BiasList bias = {first, tok, child, unc, weight, bias_sum, bias_node};
     return beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, &bias);
+}
+
+extern "C" int64_t avsr_ctc_beam_ngram_workspace_bytes(int B, int T, int W, int K, int with_bias) {
+    if (B <= 0 || T <= 0 || W <= 0 || K <= 0) return 16;
+    return (with_bias ? avsr_ctc_beam_bias_workspace_bytes(B, T, W, K) : avsr_ctc_beam_workspace_bytes(B, T, W, K)) +
+           2 * align16((int64_t)B * T * K * 4);
+}
+
+extern "C" int avsr_ctc_beam_search_ngram(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
+                                          const int32_t* first, const int32_t* tok, const int32_t* child, const int32_t* unc, int b_nodes,
+                                          int b_edges, float bias_weight, const int32_t* n_first, const int32_t* n_tok, const float* n_logp,
+                                          const int32_t* n_next, const float* n_bow, const int32_t* n_back, int n_nodes, int n_edges,
+                                          int start_node, int eos, float ngram_weight, float len_bonus, int32_t* tokens, int32_t* lens,
+                                          float* score, float* pb, float* pnb, int32_t* n_valid, float* bias_sum, int32_t* bias_node,
+                                          float* ngram_sum, int32_t* ngram_node, void* workspace, int B, int T, int V, hipStream_t stream) {
+    AVSR_REQUIRE(b_nodes >= 0 && b_nodes <= AVSR_BIAS_MAX_NODES && b_edges >= 0 && b_edges <= AVSR_BIAS_MAX_EDGES,
+                 "ctc_beam_search_ngram: too many bias nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
+    AVSR_REQUIRE(bias_weight == bias_weight && fabsf(bias_weight) <= 1e30f, "ctc_beam_search_ngram: the bias weight must be finite");
+    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_NGRAM_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_NGRAM_MAX_EDGES,
+                 "ctc_beam_search_ngram: too many nodes or edges (AVSR_NGRAM_MAX_NODES / AVSR_NGRAM_MAX_EDGES)");
+    AVSR_REQUIRE(ngram_weight == ngram_weight && fabsf(ngram_weight) <= 1e30f && len_bonus == len_bonus && fabsf(len_bonus) <= 1e30f,
+                 "ctc_beam_search_ngram: the n-gram weight and the length bonus must be finite");
+    const bool biased = b_nodes != 0 && b_edges != 0;
+    const BiasList bias = {first, tok, child, unc, bias_weight, bias_sum, bias_node};
+    if (n_nodes == 0 || n_edges == 0) {  // no model: the biased or the plain search, and nothing was scored
+        const int rc = avsr_ctc_beam_search_bias(lp, ld, in_lens, blank, W, K, nbest, first, tok, child, unc, b_nodes, b_edges, bias_weight,
+                                                 tokens, lens, score, pb, pnb, n_valid, bias_sum, bias_node, workspace, B, T, V, stream);
+        if (rc != 0 || B <= 0) return rc;
+        AVSR_LAUNCH(ctc_bias_zero_kernel, dim3((unsigned)((B * nbest + 255) / 256)), dim3(256), 0, stream, ngram_sum, ngram_node, B * nbest);
+        AVSR_CHECK_LAUNCH("ctc_beam_search_ngram");
+        return 0;
+    }
+    AVSR_REQUIRE(start_node >= 0 && start_node < n_nodes, "ctc_beam_search_ngram: start node outside the model");
+    AVSR_REQUIRE(blank == 0, "ctc_beam_search_ngram: the model's tables take the blank to be id 0");
+    AVSR_REQUIRE(eos == V - 1, "ctc_beam_search_ngram: </s> must be the last id of the vocabulary");
+    AVSR_REQUIRE(n_first && n_tok && n_logp && n_next && n_bow && n_back, "ctc_beam_search_ngram: missing table");
+    const NgramModel ng = {{n_first, n_tok, n_logp, n_next, n_bow, n_back}, start_node, eos, ngram_weight, len_bonus, ngram_sum, ngram_node};
+    const int rc = beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream,
+                               biased ? &bias : nullptr, &ng);
+    if (rc != 0 || B <= 0 || biased) return rc;
+    AVSR_LAUNCH(ctc_bias_zero_kernel, dim3((unsigned)((B * nbest + 255) / 256)), dim3(256), 0, stream, bias_sum, bias_node, B * nbest);
+    AVSR_CHECK_LAUNCH("ctc_beam_search_ngram");
+    return 0;
 }
 
 // Workspace layout: lpg[B*N*T*Smax] f32 | ext[B*N*Smax] i32 | lens[B*N] i32

@@ -124,16 +124,18 @@ def _lp_rows(lp):
     return pit
 
 
-def ctc_beam_search(lp, in_lens, blank=0, beam=16, topk=16, nbest=None, bias=None, bias_weight=0.0):
-    """CTC prefix beam search over log-posteriors [B,T,V] (csrc/ctc_beam.hip; ops.ctc_beam_search describes the result, and
-    `bias` / `bias_weight`: a ContextBiasScorer whose phrases are boosted inside the search)."""
+def ctc_beam_search(lp, in_lens, blank=0, beam=16, topk=16, nbest=None, bias=None, bias_weight=0.0, ngram=None, ngram_weight=0.0,
+                    len_bonus=0.0):
+    """CTC prefix beam search over log-posteriors [B,T,V] (csrc/ctc_beam.hip; ops.ctc_beam_search describes the result,
+    `bias` / `bias_weight`: a ContextBiasScorer whose phrases are boosted inside the search, and `ngram` / `ngram_weight` /
+    `len_bonus`: an NgramScorer whose running log-probability, with a per-token bonus, joins the key the search ranks by)."""
     with torch.no_grad():
         lp = lp.detach()
         B, Tn, V = lp.shape
         l2, ld = _lp_rows(lp)
         lens = in_lens.to(device=lp.device, dtype=torch.int64).contiguous()
         return ops.ctc_beam_search(l2, ld, lens, B, Tn, V, blank=int(blank), beam=beam, topk=topk, nbest=nbest, bias=bias,
-                                   bias_weight=bias_weight)
+                                   bias_weight=bias_weight, ngram=ngram, ngram_weight=ngram_weight, len_bonus=len_bonus)
 
 
 def ctc_score(lp, labels, in_lens, blank=0, ignore_id=-1):

@@ -539,14 +539,17 @@ class CTC(nn.Module):
         return AF.ctc_align(logits, ys_pad, hlens, blank=blank_id, ignore_id=self.ignore_id)
 
     # ---- first pass of two-pass decoding: time-synchronous prefix beam search on the device (csrc/ctc_beam.hip)
-    def prefix_beam_search(self, hs_pad, hlens, beam=16, topk=16, nbest=None, blank_id=0, bias=None, bias_weight=0.0):
+    def prefix_beam_search(self, hs_pad, hlens, beam=16, topk=16, nbest=None, blank_id=0, bias=None, bias_weight=0.0, ngram=None,
+                           ngram_weight=0.0, len_bonus=0.0):
         """Not in the reference: hidden states (B, T, D), lengths (B,) -> the n-best prefixes of a CTC prefix beam search over the
         head's log-softmax (beam entries kept per frame, `topk` non-blank tokens considered per frame), as the dict of device
         tensors of ops.ctc_beam_search: tokens (B, nbest, T) padded with -1, lens, score, pb, pnb (B, nbest), n_valid (B,).
         bias (a ContextBiasScorer of this head's vocabulary) with bias_weight != 0 boosts its phrases inside the search; the dict's
-        bias_sum / bias_node (B, nbest) are the gains each prefix keeps and its trie node."""
+        bias_sum / bias_node (B, nbest) are the gains each prefix keeps and its trie node.  ngram (an NgramScorer of this head's
+        vocabulary) with ngram_weight != 0 adds ngram_weight * (the model's running log-probability) + len_bonus * (tokens) to the key
+        the search ranks by; the dict's ngram_sum / ngram_node (B, nbest) are the model's term of each finished prefix and its node."""
         return AF.ctc_beam_search(self.log_softmax(hs_pad), hlens, blank=blank_id, beam=beam, topk=topk, nbest=nbest, bias=bias,
-                                  bias_weight=bias_weight)
+                                  bias_weight=bias_weight, ngram=ngram, ngram_weight=ngram_weight, len_bonus=len_bonus)
 
     def forced_align(self, h, y, blank_id=0):
         """ctc.py:95-158: hidden states (T, D) or (1, T, D), id sequence (L,) -> list of T token ids (python ints)."""

@@ -1,6 +1,7 @@
 """Thin Python wrappers over the C ABI (include/avsr_hip.h): one function per entry point,
 taking torch tensors as device-memory handles.  No compute happens in Python or ATen here."""
 import contextlib
+import math
 import os
 
 import torch
@@ -614,7 +615,8 @@ def _zeros_view(shape, dtype, dev):
     return z.expand(shape)
 
 
-def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=None, bias=None, bias_weight=0.0):
+def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=None, bias=None, bias_weight=0.0, ngram=None,
+                    ngram_weight=0.0, len_bonus=0.0):
     """CTC prefix beam search (csrc/ctc_beam.hip).  lp: f32 [B*T, ld] log-posteriors; in_lens int64 [B].  Returns a dict of
     device tensors: tokens int32 [B, nbest, T] (-1 padded), lens int32 [B, nbest], score / pb / pnb f32 [B, nbest], n_valid int32
     [B], and the history of the search as views of its workspace (ctc_beam_trace rebuilds the per-frame beams from them):
@@ -623,20 +625,49 @@ def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=N
     bias (an auto_avsr_amd.bias.ContextBiasScorer) with bias_weight != 0: contextual biasing, avsr_ctc_beam_search_bias -- a frame
     keeps the prefixes of largest total + bias_weight * (sum of the prefix' gains); every mass above stays pure CTC.  The dict always
     carries bias_sum f32 [B, nbest] (the gains a finished hypothesis keeps) and bias_node int32 [B, nbest]; bias None or bias_weight 0
-    is the plain call, with the launches it always had: the two are then read-only zeros (stride-0 views, no fill is launched)."""
+    is the plain call, with the launches it always had: the two are then read-only zeros (stride-0 views, no fill is launched).
+    ngram (an auto_avsr_amd.ngram.NgramScorer over the same vocabulary) with ngram_weight != 0: the back-off n-gram model inside the
+    search, avsr_ctc_beam_search_ngram -- the key of a prefix gains ngram_weight * G(prefix) + len_bonus * len(prefix), G the model's
+    running f32 sum of log-probabilities; it needs blank == 0.  The dict always carries ngram_sum f32 [B, nbest] (G + log p(</s>), equal
+    to ngram.walk(prefix + [eos])[0] bit for bit) and ngram_node int32 [B, nbest]; without a model they are read-only zeros and the
+    call, the workspace and the launches are those of the search without it.  len_bonus without a model is a ValueError."""
     W, K = int(beam), int(topk)
     nbest = W if nbest is None else int(nbest)
     dev = lp.device
     biased = bias is not None and float(bias_weight) != 0.0
-    ws_bytes = call("avsr_ctc_beam_bias_workspace_bytes" if biased else "avsr_ctc_beam_workspace_bytes", B, T, W, K)
+    fused = ngram is not None and float(ngram_weight) != 0.0
+    if not fused and float(len_bonus) != 0.0:
+        raise ValueError("ctc_beam_search: len_bonus belongs to the n-gram model (ngram with ngram_weight != 0)")
+    if fused:
+        if ngram.n_vocab != V:
+            raise ValueError(f"ctc_beam_search: the n-gram model's vocabulary ({ngram.n_vocab}) is not the posteriors' ({V})")
+        if int(blank) != 0:
+            raise ValueError("ctc_beam_search: the n-gram model's tables take the blank to be id 0")
+        if not (math.isfinite(float(ngram_weight)) and math.isfinite(float(len_bonus))):
+            raise ValueError("ctc_beam_search: ngram_weight and len_bonus must be finite")
+    if fused:
+        ws_bytes = call("avsr_ctc_beam_ngram_workspace_bytes", B, T, W, K, int(biased))
+    else:
+        ws_bytes = call("avsr_ctc_beam_bias_workspace_bytes" if biased else "avsr_ctc_beam_workspace_bytes", B, T, W, K)
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
     tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
     lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
     n_valid = torch.empty(B, dtype=torch.int32, device=dev)
     score, pb, pnb = (torch.empty(B, nbest, dtype=torch.float32, device=dev) for _ in range(3))
-    if biased:
-        if bias.n_vocab != V:
-            raise ValueError(f"ctc_beam_search: the bias scorer's vocabulary ({bias.n_vocab}) is not the posteriors' ({V})")
+    if biased and bias.n_vocab != V:
+        raise ValueError(f"ctc_beam_search: the bias scorer's vocabulary ({bias.n_vocab}) is not the posteriors' ({V})")
+    ngram_sum, ngram_node = _zeros_view((B, nbest), torch.float32, dev), _zeros_view((B, nbest), torch.int32, dev)
+    if fused:
+        bias_sum, ngram_sum = (torch.empty(B, nbest, dtype=torch.float32, device=dev) for _ in range(2))
+        bias_node, ngram_node = (torch.empty(B, nbest, dtype=torch.int32, device=dev) for _ in range(2))
+        btabs = bias.device_tables(dev) if biased else (None,) * 4
+        ntabs = ngram.device_tables(dev)  # (the scorers keep them alive)
+        call("avsr_ctc_beam_search_ngram", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, *[_ptr(t) for t in btabs],
+             bias.n_nodes if biased else 0, bias.n_edges if biased else 0, float(bias_weight) if biased else 0.0,
+             *[_ptr(t) for t in ntabs], ngram.n_nodes, ngram.n_edges, int(ngram.start_node), V - 1, float(ngram_weight), float(len_bonus),
+             _ptr(tokens), _ptr(lens), _ptr(score), _ptr(pb), _ptr(pnb), _ptr(n_valid), _ptr(bias_sum), _ptr(bias_node), _ptr(ngram_sum),
+             _ptr(ngram_node), _ptr(ws), B, T, V, _stream(lp))
+    elif biased:
         bias_sum = torch.empty(B, nbest, dtype=torch.float32, device=dev)
         bias_node = torch.empty(B, nbest, dtype=torch.int32, device=dev)
         tabs = bias.device_tables(dev)  # (the scorer keeps them alive)
@@ -648,7 +679,7 @@ def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=N
         call("avsr_ctc_beam_search", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, _ptr(tokens), _ptr(lens), _ptr(score),
              _ptr(pb), _ptr(pnb), _ptr(n_valid), _ptr(ws), B, T, V, _stream(lp))
     out = {"tokens": tokens, "lens": lens, "score": score, "pb": pb, "pnb": pnb, "n_valid": n_valid, "beam": W, "topk": K,
-           "bias_sum": bias_sum, "bias_node": bias_node}
+           "bias_sum": bias_sum, "bias_node": bias_node, "ngram_sum": ngram_sum, "ngram_node": ngram_node}
     if T > 0:
         o = 0
         for name, shape, as_f32 in (("topk_tok", (B, T, K), False), ("topk_val", (B, T, K), True), ("blank_val", (B, T), True),

@@ -15,7 +15,18 @@ maxlen dependent decoder steps per utterance; here the only chain is the T frame
 Contextual biasing (`scorers["bias"]`, a ContextBiasScorer, with `weights["bias"]`): the first pass ranks its prefixes by CTC total +
 weight * (gains so far), which pulls the expected phrases into the beam (a boosted token still has to be among the frame's `topk`
 tokens), and the objective carries the bias term of the label-synchronous search; the term of the n-best comes back from the first
-pass itself.  The scorer is read at every call: `set_phrases` between utterances needs no rebuild."""
+pass itself.  The scorer is read at every call: `set_phrases` between utterances needs no rebuild.
+
+Back-off n-gram model (`scorers["ngram"]`, an NgramScorer, with `weights["ngram"]`; `set_ngram` swaps it between calls): the first pass
+ranks its prefixes by CTC total (+ bias) + weight * G(prefix) + len_bonus * len(prefix), G the model's running sum of
+log-probabilities -- the time-synchronous search of every CTC + n-gram decoder, with its per-token bonus against the deletions a sum of
+negative terms favours --, and the objective carries
+
+               + ngram_weight * sum_{i <= L+1} log p_ng(y_i | y_<i)
+
+which is what the hybrid search stores in scores["ngram"] for a hypothesis that ended with a scored <eos>.  The term of the n-best
+comes back from the first pass (bit for bit the host walk); `rescore` walks sequences given from outside on the host.  len_bonus only
+steers the first pass: it is no term of the objective (`length_bonus` is)."""
 from typing import List
 
 import torch
@@ -28,10 +39,11 @@ from .decoding import Hypothesis
 class TwoPassDecoder:
     """A plain object (it owns no parameters: the scorers stay where they are).  Drop-in for BatchBeamSearch where it is called
     (`__call__(enc)`, `forward_many(encs)`): the same scorer / weight dictionaries as lightning.get_beam_search_decoder builds -- `decoder` (TransformerDecoder), `ctc` (the CTC head or its CTCPrefixScorer),
-    optional `lm` (TransformerLM), optional `bias` (ContextBiasScorer), optional `length_bonus` (only its weight is used) -- and lists of decoding.Hypothesis, best first,
+    optional `lm` (TransformerLM), optional `bias` (ContextBiasScorer), optional `ngram` (NgramScorer), optional `length_bonus` (only its weight is used) -- and lists of decoding.Hypothesis, best first,
     with yseq = [sos, y..., eos] and one `scores` entry per scorer of non-zero weight."""
 
-    def __init__(self, scorers, weights, sos, eos, token_list=None, beam_size=16, topk=16, nbest=None, blank=0, ignore_id=-1):
+    def __init__(self, scorers, weights, sos, eos, token_list=None, beam_size=16, topk=16, nbest=None, blank=0, ignore_id=-1,
+                 len_bonus=0.0):
         self.weights = {k: float(v) for k, v in weights.items()}
         self.scorers = {k: v for k, v in scorers.items() if v is not None and self.weights.get(k, 0.0) != 0.0}
         ctc = scorers.get("ctc")
@@ -51,9 +63,31 @@ class TwoPassDecoder:
 
             if not isinstance(self.bias, ContextBiasScorer) or self.bias.n_vocab != self.n_vocab:
                 raise TypeError(f"bias: an auto_avsr_amd.bias.ContextBiasScorer over the CTC head's vocabulary ({self.n_vocab})")
+        self.ngram, self.len_bonus = None, 0.0
+        self.set_ngram(self.scorers.get("ngram"), self.weights.get("ngram", 0.0), len_bonus)
         self.beam_size, self.topk = int(beam_size), min(int(topk), self.n_vocab - 1)
         self.nbest = self.beam_size if nbest is None else int(nbest)
         self.last_first_pass = None  # the first pass' result of the latest call (tools / tests)
+
+    def set_ngram(self, scorer, weight, len_bonus=None):
+        """Set, replace or (scorer None or weight 0) remove the n-gram model; len_bonus None keeps the bonus it has.  Takes effect at
+        the next call: nothing is cached here."""
+        from .ngram import NgramScorer
+
+        weight = float(weight)
+        lb = self.len_bonus if len_bonus is None else float(len_bonus)
+        if scorer is None or weight == 0.0:
+            self.ngram, self.len_bonus = None, lb
+            self.scorers.pop("ngram", None)
+            self.weights["ngram"] = 0.0
+            return
+        if not isinstance(scorer, NgramScorer) or scorer.n_vocab != self.n_vocab:
+            raise TypeError(f"ngram: an auto_avsr_amd.ngram.NgramScorer over the CTC head's vocabulary ({self.n_vocab})")
+        if self.blank != 0 or self.eos != self.n_vocab - 1:
+            raise ValueError("ngram: the model's tables need blank == 0 and eos == n_vocab - 1")
+        self.ngram, self.len_bonus = scorer, lb
+        self.scorers["ngram"] = scorer
+        self.weights["ngram"] = weight
 
     # ------------------------------------------------------------------------------------------------ pieces
     def _posteriors(self, encs):
@@ -65,7 +99,8 @@ class TwoPassDecoder:
     def first_pass(self, lp, hlens):
         """The n-best prefixes per utterance as label rows padded with ignore_id: (labels int64 [B, N, Lmax], n_valid list)."""
         res = AF.ctc_beam_search(lp, hlens, blank=self.blank, beam=self.beam_size, topk=self.topk, nbest=self.nbest, bias=self.bias,
-                                 bias_weight=self.weights.get("bias", 0.0))
+                                 bias_weight=self.weights.get("bias", 0.0), ngram=self.ngram, ngram_weight=self.weights.get("ngram", 0.0),
+                                 len_bonus=self.len_bonus if self.ngram is not None else 0.0)
         self.last_first_pass = res
         Lmax = max(1, int(res["lens"].max()))
         return res["tokens"][:, :, :Lmax].to(torch.int64).contiguous(), res["n_valid"].tolist()
@@ -88,10 +123,16 @@ class TwoPassDecoder:
             rows.append(float(g + self.bias.step(s, self.eos)[0]))
         return torch.tensor(rows, dtype=torch.float32).view(labels.shape[:2]).to(labels.device)
 
-    def score_labels(self, memory, hlens, lp, labels, bias_sum=None):
+    def _ngram_sums(self, labels):
+        """The n-gram term of labels [B, N, Lmax] on the host: the model's f32 walk along each row and its <eos>."""
+        rows = [float(self.ngram.walk([t for t in row if t != self.ignore_id] + [self.eos])[0])
+                for row in labels.reshape(-1, labels.shape[-1]).tolist()]
+        return torch.tensor(rows, dtype=torch.float32).view(labels.shape[:2]).to(labels.device)
+
+    def score_labels(self, memory, hlens, lp, labels, bias_sum=None, ngram_sum=None):
         """The terms of the objective for labels [B, N, Lmax] (padded with ignore_id) of the utterances memory [B, T, D]: a dict of
         [B, N] tensors -- `score` and one entry per scorer of non-zero weight.  bias_sum [B, N]: the bias term where the first pass
-        already has it; None: walked on the host."""
+        already has it; None: walked on the host.  ngram_sum [B, N]: the same for the n-gram term."""
         B, N, Lmax = labels.shape
         dev = memory.device
         out = {}
@@ -111,8 +152,10 @@ class TwoPassDecoder:
             out["length_bonus"] = n_tok
         if self.bias is not None:
             out["bias"] = self._bias_sums(labels) if bias_sum is None else bias_sum.to(torch.float32)
+        if self.ngram is not None:
+            out["ngram"] = self._ngram_sums(labels) if ngram_sum is None else ngram_sum.to(torch.float32)
         total = torch.zeros(B, N, dtype=torch.float32, device=dev)
-        for k in ("decoder", "lm", "bias", "length_bonus", "ctc"):
+        for k in ("decoder", "lm", "bias", "ngram", "length_bonus", "ctc"):
             if k in out:
                 total = total + self.weights[k] * out[k]
         out["score"] = total
@@ -159,7 +202,8 @@ class TwoPassDecoder:
             return []
         memory, hlens, lp = self._posteriors(xs)
         labels, n_valid = self.first_pass(lp, hlens)
-        terms = self.score_labels(memory, hlens, lp, labels, bias_sum=self.last_first_pass["bias_sum"] if self.bias is not None else None)
+        terms = self.score_labels(memory, hlens, lp, labels, bias_sum=self.last_first_pass["bias_sum"] if self.bias is not None else None,
+                                  ngram_sum=self.last_first_pass["ngram_sum"] if self.ngram is not None else None)
         labels = labels.cpu()
         terms = {k: v.cpu() for k, v in terms.items()}
         return [self._hypotheses(labels, terms, b, max(1, int(n_valid[b]))) for b in range(len(xs))]

@@ -319,6 +319,33 @@ int avsr_ctc_beam_search_bias(const float* lp, int64_t ld, const int64_t* in_len
                               const int32_t* first, const int32_t* tok, const int32_t* child, const int32_t* unc, int n_nodes, int n_edges,
                               float weight, int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid,
                               float* bias_sum, int32_t* bias_node, void* workspace, int B, int T, int V, avsr_stream_t stream);
+/* The same search, plain or biased, with a back-off n-gram language model (the tables and the lookup rule of avsr_ngram_score /
+ * avsr_beam_set_ngram below: n_first [n_nodes + 1], n_tok / n_logp / n_next [n_edges], n_bow / n_back [n_nodes], device tables owned by
+ * the caller that outlive the call; ONE model for all utterances of the launch).  Every beam entry carries the model's node of its
+ * prefix, reached from start_node, and the running f32 sum G of the log-probabilities of its tokens (G' = G + r per token, r summed in
+ * the lookup's fixed order); a staying candidate keeps both.  A frame keeps the W prefixes of largest
+ *   logaddexp(pb, pnb) + bias_weight * (sum of gains) + ngram_weight * G + len_bonus * len(prefix)
+ * (the bias term only with a list; len_bonus is the per-token bonus that keeps negative log-probabilities from favouring deletions).
+ * Nothing else sees the model: pb / pnb of the recursion, score / pb / pnb of the outputs and the beam records stay pure CTC masses, a
+ * prefix without mass stays dead, a token still has to be among the frame's K tokens, and the n-best is the last beam in its key order.
+ * Beside the outputs of avsr_ctc_beam_search_bias it returns ngram_sum f32 [B][nbest] = G + log p(eos | node), the model's term of a
+ * finished hypothesis, and ngram_node int32 [B][nbest], the node of the prefix; both 0 beyond n_valid[b].  The workspace
+ * (avsr_ctc_beam_ngram_workspace_bytes, 16-byte aligned) is the plain layout (with_bias: the biased one) followed by
+ *   ulogp f32 [B][T][K], unext int32 [B][T][K]  (each padded to 16 bytes) the root's log-probability of each of the frame's tokens and
+ *                          the node reached (resolved by a launch of its own before the search: every back-off walk ends there, so
+ *                          only the levels below the root are read inside the frame loop)
+ * n_nodes == 0 or n_edges == 0: exactly avsr_ctc_beam_search_bias, ngram_sum / ngram_node zero-filled.  b_nodes == 0 or b_edges == 0:
+ * no list, bias_sum / bias_node zero-filled.  With a model the library requires blank == 0 (the root has an edge on every other
+ * token), eos == V - 1, 0 <= start_node < n_nodes, table sizes within AVSR_NGRAM_MAX_NODES / AVSR_NGRAM_MAX_EDGES and finite
+ * ngram_weight / len_bonus; the contents of the tables are the caller's responsibility, as for avsr_beam_set_ngram. */
+int64_t avsr_ctc_beam_ngram_workspace_bytes(int B, int T, int W, int K, int with_bias);
+int avsr_ctc_beam_search_ngram(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
+                               const int32_t* first, const int32_t* tok, const int32_t* child, const int32_t* unc, int b_nodes, int b_edges,
+                               float bias_weight, const int32_t* n_first, const int32_t* n_tok, const float* n_logp, const int32_t* n_next,
+                               const float* n_bow, const int32_t* n_back, int n_nodes, int n_edges, int start_node, int eos,
+                               float ngram_weight, float len_bonus, int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb,
+                               int32_t* n_valid, float* bias_sum, int32_t* bias_node, float* ngram_sum, int32_t* ngram_node,
+                               void* workspace, int B, int T, int V, avsr_stream_t stream);
 /* Exact CTC log-likelihood of N label sequences per utterance against ONE copy of its log-posteriors: lp f32 [B][T][ld]; labels
  * int64 [B][N][Lmax] padded with ignore_id (Lmax <= 255); loglik f32 [B][N] = log P_ctc(labels | lp[b, :in_lens[b]]); no labels:
  * the sum of lp[t][blank]; a sequence that does not fit the frames: -inf. */

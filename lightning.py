@@ -371,9 +371,15 @@ class ModelModule(_Base):
         lm_path, lm_weight = getattr(args, "lm_path", None), float(getattr(args, "lm_weight", 0.0) or 0.0)
         make = get_beam_search_decoder
         if getattr(args, "decode_mode", "search") == "rescore":  # eval.py --decode-mode rescore: two-pass decoding
-            def make(model, token_list, **kw):
-                return get_two_pass_decoder(model, token_list, beam_size=int(getattr(args, "rescore_beam", None) or 16),
-                                            topk=int(getattr(args, "rescore_topk", None) or 16), **kw)
+            def make(model, token_list, ngram=None, ngram_weight=0.0, **kw):
+                # the getter still refuses its n-gram keyword (pinned by tests): the model goes in through set_ngram, with the per-token
+                # bonus of the first pass (args.rescore_len_bonus)
+                tp = get_two_pass_decoder(model, token_list, beam_size=int(getattr(args, "rescore_beam", None) or 16),
+                                          topk=int(getattr(args, "rescore_topk", None) or 16), **kw)
+                sc = _resolve_ngram(token_list, ngram, ngram_weight, what="rescoring")
+                if sc is not None:
+                    tp.set_ngram(sc, ngram_weight, len_bonus=float(getattr(args, "rescore_len_bonus", 0.0) or 0.0))
+                return tp
         kw = {}
         bias = self._bias_scorer()
         if bias is not None:  # (either decoder takes it; eval.py's parse_args still refuses the flags with --decode-mode rescore)
@@ -549,8 +555,8 @@ def get_two_pass_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty
     from espnet.nets.scorers.length_bonus import LengthBonus
 
     if ngram is not None or ngram_weight != 0.0:
-        raise NotImplementedError("two-pass decoding takes no n-gram model: neither the CTC prefix beam search of the first pass nor the "
-                                  "rescoring objective has the term; use get_beam_search_decoder(ngram=..., ngram_weight=...)")
+        raise NotImplementedError("get_two_pass_decoder takes no n-gram keyword: give the decoder its n-gram model with "
+                                  "TwoPassDecoder.set_ngram(scorer, weight, len_bonus) (ModelModule does, from args.ngram_path)")
     lm = _resolve_lm(model, token_list, rnnlm, rnnlm_conf, lm_weight, what="rescoring")
     bias = _resolve_bias(token_list, bias_phrases, bias_weight, what="rescoring")
     sos = eos = model.odim - 1

@@ -48,7 +48,11 @@ def main():
     ap.add_argument("--ngram", action="store_true",
                     help="n-gram shallow-fusion rows instead of the default ones: a random 3-gram back-off model of about 10^6 n-grams, weight "
                          "0.3 -- the native step without and with it, and the python-issued step with it, sides alternated "
-                         "(precise mode; python tools/bench_decode.py --ngram > profiles/ngram_decode.json)")
+                         "(precise mode; python tools/bench_decode.py --ngram > profiles/ngram_decode.json).  With --two-pass: two-pass decoding "
+                         "without and with the same model inside the first pass, alternated -- first pass and whole decode "
+                         "(python tools/bench_decode.py --two-pass --ngram --reps 30 > profiles/two_pass_ngram_decode.json).  With "
+                         "--two-pass-sweep: the trained fixture's sweep, then with a 3-gram estimated from the fixture's own transcripts "
+                         "(python tools/bench_decode.py --two-pass-sweep --ngram > profiles/two_pass_ngram_sweep.json)")
     ap.add_argument("--encode", action="store_true",
                     help="encoder-only rows instead of the default ones: 16 utterances around T = 100 and around T = 400 frames (lengths spread "
                          "+-20 %) through ModelModule.encode_many one at a time and in zero-padded groups of 4, 8 and 16, alternated, precise "
@@ -74,6 +78,8 @@ def main():
         return main_two_pass_bias(args)
     if args.bias:
         return main_bias(args)
+    if args.ngram and args.two_pass:
+        return main_two_pass_ngram(args)
     if args.ngram:
         return main_ngram(args)
     if args.two_pass or args.two_pass_once:
@@ -834,6 +840,150 @@ def main_two_pass_bias(args):
                       "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
 
 
+def main_two_pass_ngram(args):
+    import random
+    import statistics
+
+    import lightning
+    from synth import synth_batch, synth_state_dict
+
+    from auto_avsr_amd import functional as AF
+    from auto_avsr_amd.e2e import E2E
+    from auto_avsr_amd.ngram import NgramScorer
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode.py --two-pass --ngram needs an MI355X: there is nothing to time without one")
+    dev = torch.device("cuda:0")
+    V = 5049
+    m = E2E(V, "video")
+    m.load_state_dict(synth_state_dict(m.state_dict(), 3))
+    m = m.to(dev).eval()
+    toks = [str(i) for i in range(V)]
+    w_ngram, len_bonus = 0.3, 0.5
+    AF.set_mode("precise")
+    mk = lambda: lightning.get_two_pass_decoder(m, toks, beam_size=args.rescore_beam, topk=args.rescore_topk)  # noqa: E731
+    plain = mk()
+    encs, firsts = {}, {}
+    for T in (100, 400):
+        x, _, _ = synth_batch("video", 1, T, 3, V, seed=T, lengths=[T])
+        with torch.no_grad():
+            encs[T] = m.encoder(m.proj_encoder(m.frontend(x.to(dev))), None)[0].squeeze(0).float()
+            _, hlens, lp = plain._posteriors([encs[T]])
+            plain.first_pass(lp, hlens)
+        res = plain.last_first_pass
+        firsts[T] = res["tokens"][0, 0, : int(res["lens"][0, 0])].tolist()
+    # the random 3-gram model of --ngram (about 10^6 n-grams); random contexts never meet a hypothesis, so the n-grams of the model-free
+    # first-pass winners are part of it: the search then stands at bigram contexts and backs off from them (the rest is the model's bulk)
+    rng = random.Random(11)
+    P = {(t,): -rng.uniform(2.0, 9.0) for t in range(1, V)}
+    P[(V,)] = -99.0
+    B = {(V,): -0.5}
+    seqs = [[V] + [t for t in f if t != V - 1] + [V - 1] for f in firsts.values()]
+    bis = {tuple(q[i: i + 2]) for q in seqs for i in range(len(q) - 1)}
+    while len(bis) < 330000:
+        bis.add((rng.randint(1, V - 2), rng.randint(1, V - 1)))
+    bis = sorted(bis)
+    inner = [g for g in bis if g[1] != V - 1]
+    tris = {tuple(q[i: i + 3]) for q in seqs for i in range(len(q) - 2)}
+    while len(tris) < 665000:
+        tris.add(rng.choice(inner) + (rng.randint(1, V - 1),))
+    for g in bis:
+        P[g] = -rng.uniform(0.1, 6.0)
+        B.setdefault((g[0],), -rng.uniform(0.05, 2.0))
+    for g in tris:
+        P[g] = -rng.uniform(0.1, 5.0)
+        B.setdefault(g[:2], -rng.uniform(0.05, 2.0))
+    sc = NgramScorer(V, P, B, order=3)
+    fused = mk()
+    fused.set_ngram(sc, w_ngram, len_bonus=len_bonus)
+    sides = {"no_model": plain, "with_model": fused}
+    rows = []
+    for T in (100, 400):
+        enc = encs[T]
+        with torch.no_grad():
+            _, hlens, lp = plain._posteriors([enc])
+        times, out, rows_of, failed = {k: {"first_pass": [], "whole_decode": []} for k in sides}, {}, {}, {}
+        for rep_ in range(args.reps + 1):  # first repetition = warm-up; the sides alternate within a repetition
+            for k, tp in sides.items():
+                for what, fn in (("first_pass", lambda: tp.first_pass(lp, hlens)), ("whole_decode", lambda: tp(enc))):
+                    if (k, what) in failed:
+                        continue
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    try:
+                        with torch.no_grad():
+                            res = fn()
+                    except RuntimeError as e:  # (the rescoring pass takes label rows of at most 255 tokens)
+                        failed[(k, what)] = str(e)
+                        continue
+                    torch.cuda.synchronize()
+                    if rep_:
+                        times[k][what].append((time.perf_counter() - t0) * 1e3)
+                    if what == "first_pass":
+                        rows_of[k] = int(res[0].shape[2])
+                    else:
+                        out[k] = res
+        fp = fused.last_first_pass
+        row = {"T_frames": T, "beam": args.rescore_beam, "topk": args.rescore_topk, "mode": "precise", "vocabulary": V, "ngram_weight": w_ngram,
+               "len_bonus": len_bonus, "order": sc.order, "ngrams": len(P), "nodes": sc.n_nodes, "edges": sc.n_edges,
+               "winner_lookup": "(G', next) of every extension kept in LDS for the frame's winners (no bias list: 65 120 bytes of LDS)", "repetitions": args.reps,
+               "nbest_rows_below_the_root": int((fp["ngram_node"][0] != 0).sum()), "sides": {}}
+        for k in sides:
+            row["sides"][k] = {what + "_ms": None if (k, what) in failed else
+                               {"median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
+                               for what, ts in times[k].items()}
+            row["sides"][k]["longest_label_row"] = rows_of[k]
+            row["sides"][k]["best_ngram_sum"] = out[k][0].asdict()["scores"].get("ngram") if k in out else None
+            for what in ("first_pass", "whole_decode"):
+                if (k, what) in failed:
+                    row["sides"][k][what + "_error"] = failed[(k, what)]
+        for what in ("first_pass", "whole_decode"):
+            if any((k, what) in failed for k in sides):
+                continue
+            a, b = (row["sides"][k][what + "_ms"]["median"] for k in ("no_model", "with_model"))
+            row[f"model_cost_{what}_ms"] = round(b - a, 3)
+            row[f"model_cost_{what}_relative"] = round(b / a - 1.0, 4)
+        if len(out) == 2:
+            row["model_changes_best"] = out["with_model"][0].asdict()["yseq"] != out["no_model"][0].asdict()["yseq"]
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    AF.set_mode("bf16")
+    print(json.dumps({"metric": "back-off n-gram model in two-pass decoding: CTC prefix beam search on the device (first pass) and the whole "
+                                "decode (posteriors + first pass + teacher-forced rescoring) without and with a random 3-gram model of about "
+                                "10^6 n-grams (plus the n-grams of the model-free first-pass winners); video E2E 250M, one utterance per "
+                                "launch, encoder output ready, wall clock between synchronisations, one warm-up then the sides alternated",
+                      "data": "synthetic input, synthetic (tests/golden/synth.py) weights", "rows": rows}))
+
+
+def _fixture_trigram(labels, V):
+    """A 3-gram estimated on the host from token-id transcripts: absolute discounting (0.5) with back-off to the lower order, add-0.1
+    unigrams over the whole vocabulary.  {n-gram: ln p}, {context: ln back-off}; <s> = V, </s> = V - 1."""
+    import math
+    from collections import Counter, defaultdict
+
+    D = 0.5
+    uni, ctx = Counter(), {2: defaultdict(Counter), 3: defaultdict(Counter)}
+    for y in labels:
+        q = [V] + [int(t) for t in y] + [V - 1]
+        uni.update(q[1:])
+        for n in (2, 3):
+            for i in range(len(q) - n + 1):
+                ctx[n][tuple(q[i: i + n - 1])][q[i + n - 1]] += 1
+    total = sum(uni.values()) + 0.1 * (V - 1)
+    P = {(t,): math.log((uni.get(t, 0) + 0.1) / total) for t in range(1, V)}
+    P[(V,)] = -99.0
+    B = {}
+    for n in (2, 3):
+        for h, nxt in ctx[n].items():
+            if n == 3 and h not in P:  # (its own context must be an entry one order lower)
+                continue
+            c = sum(nxt.values())
+            for w, k in nxt.items():
+                P[h + (w,)] = math.log((k - D) / c)
+            B[h] = math.log(D * len(nxt) / c)
+    return P, B
+
+
 def main_two_pass_sweep(args):
     import lightning
     import trained_common as TC
@@ -876,6 +1026,29 @@ def main_two_pass_sweep(args):
                      "winner_scores_at_least_reference_best": ge, "winner_is_reference_best": same,
                      "one_launch_ms_all_utterances_incl_first_call_overheads": round(dt * 1e3, 1)})
         print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    if args.ngram:  # --two-pass-sweep --ngram: the same sweep with an IN-DOMAIN 3-gram (estimated from the fixture's own transcripts)
+        from auto_avsr_amd.ngram import NgramScorer
+
+        P, B = _fixture_trigram([u["label"] for u in fx["utts"]], TC.ODIM)
+        sc = NgramScorer(TC.ODIM, P, B, order=3)
+        for W, K in ((16, 16), (32, 16)):
+            for w, lb in ((0.0, 0.0), (0.3, 0.0), (0.3, 0.5), (0.5, 1.0), (1.0, 1.0), (1.0, 2.0)):
+                tp = lightning.get_two_pass_decoder(m, toks, beam_size=W, topk=K)
+                tp.set_ngram(sc if w else None, w, len_bonus=lb if w else 0.0)
+                with torch.no_grad():
+                    out = tp.forward_many(encs)
+                dist, dist_first, contained = 0, 0, 0
+                fp = tp.last_first_pass
+                for b, (u, nbest) in enumerate(zip(fx["utts"], out)):
+                    dist += TC.edit_distance(u["label"], [int(t) for t in nbest[0].asdict()["yseq"][1:-1]])
+                    dist_first += TC.edit_distance(u["label"], fp["tokens"][b, 0, : int(fp["lens"][b, 0])].tolist())
+                    contained += any(h.yseq.tolist() == u["hyps"][0]["yseq"] for h in nbest)
+                rows.append({"beam": W, "topk": K, "nbest": W, "ngram_weight": w, "len_bonus": lb if w else 0.0,
+                             "model": "3-gram estimated from the fixture's own reference transcripts (in-domain: a sanity ceiling)" if w else None,
+                             "nodes": sc.n_nodes if w else 0, "edges": sc.n_edges if w else 0, "wer": round(dist / fx["total_length"], 4),
+                             "first_pass_best_wer": round(dist_first / fx["total_length"], 4), "reference_search_wer": round(fx["wer"], 4),
+                             "utterances": len(fx["utts"]), "reference_best_in_nbest": contained})
+                print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
     AF.set_mode("bf16")
     print(json.dumps({"metric": "two-pass decoding on the trained fixture (32 utterances, T = 12 ... 400, reference search: beam 40)", "rows": rows}))
 
