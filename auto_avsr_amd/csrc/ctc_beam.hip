@@ -42,6 +42,7 @@
 #include "prims.h"
 #include "avsr_hip.h"
 #include "ctc_common.h"
+#include "search_tables.h"
 
 namespace {
 
@@ -150,86 +151,24 @@ __global__ __launch_bounds__(TK_NT) void ctc_topk_kernel(const float* __restrict
 
 // ---- contextual biasing: per (utterance, frame, token slot) the root's child on that token, -1 if the root has no such edge
 __global__ __launch_bounds__(256) void ctc_root_child_kernel(const int32_t* __restrict__ tok, const int64_t* __restrict__ in_lens,
-                                                             const int32_t* __restrict__ b_first, const int32_t* __restrict__ b_tok,
-                                                             const int32_t* __restrict__ b_child, int K, int Tlen, long total,
-                                                             int32_t* __restrict__ rootc) {
+                                                             BiasTab t, int K, int Tlen, long total, int32_t* __restrict__ rootc) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const long row = i / K;
     if ((int64_t)(row % Tlen) >= in_lens[row / Tlen]) return;  // (no token set was written for this frame)
-    const int v = tok[i];
-    int lo = b_first[0], hi = b_first[1], found = -1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1, x = b_tok[mid];
-        if (x == v) {
-            found = b_child[mid];
-            break;
-        }
-        if (x < v) lo = mid + 1;
-        else hi = mid;
-    }
-    rootc[i] = found;
+    const int e = tab_edge(t.first, t.tok, 0, tok[i]);
+    rootc[i] = e >= 0 ? t.child[e] : -1;
 }
 
 // ---- n-gram model: per (utterance, frame, token slot) the root's log-probability of the token and the node reached
-struct NgramTabs {
-    const int32_t *first, *tok;
-    const float* logp;
-    const int32_t* next;
-    const float* bow;
-    const int32_t* back;
-};
-// edge of node s on token v, -1 if there is none (tok[] ascending within a node).  A plain binary search: one workgroup's scattered
-// loads are bounded by the number of load instructions rather than by their latency -- a search that narrows by 8 with 7 probes in
-// flight, and level headers requested a level ahead, measured 12 % slower on the first pass than this one.
-AVSR_DEV int ng_edge(const NgramTabs& g, int s, int v) {
-    int lo = g.first[s], hi = g.first[s + 1];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1, x = g.tok[mid];
-        if (x == v) return mid;
-        if (x < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return -1;
-}
-// the root's edge on v: NgramScorer's root holds the tokens 1 .. V - 1 in order, so the edge is tried at its place first
-AVSR_DEV int ng_root_edge(const NgramTabs& g, int v) {
-    const int lo = g.first[0], hi = g.first[1], e = lo + v - 1;
-    if (e >= lo && e < hi && g.tok[e] == v) return e;
-    return ng_edge(g, 0, v);
-}
-// log p(v | node s) and the node reached, the f32 additions in the order of ngram.py: walk s, back[s], ... to the first node with an
-// edge e on v; logp[e] if that is s itself, else r = bow[s0]; r += bow[s1]; ...; r += logp[e].  (ur, un): the root's (logp, next) on
-// v, resolved by the caller, so the levels below the root are all this reads.  The walk is cut after AVSR_NGRAM_MAX_ORDER hops
-// (tables are not validated: a cycle in back[] must not hang the search).  Additions only: there is nothing to contract.
-AVSR_DEV float ng_lookup(const NgramTabs& g, int s, int v, float ur, int un, int& next) {
-    float r = 0.f;
-    bool fresh = true;
-    for (int hop = 0; s != 0 && hop < AVSR_NGRAM_MAX_ORDER; hop++) {
-        const int e = ng_edge(g, s, v);
-        if (e >= 0) {
-            next = g.next[e];
-            return fresh ? g.logp[e] : r + g.logp[e];
-        }
-        r = fresh ? g.bow[s] : r + g.bow[s];
-        fresh = false;
-        s = g.back[s];
-    }
-    if (s != 0) {
-        next = 0;
-        return r;
-    }
-    next = un;
-    return fresh ? ur : r + ur;
-}
 __global__ __launch_bounds__(256) void ctc_ngram_root_kernel(const int32_t* __restrict__ tok, const int64_t* __restrict__ in_lens,
-                                                             NgramTabs g, int K, int Tlen, long total, float* __restrict__ ulogp,
+                                                             NgramTab g, int K, int Tlen, long total, float* __restrict__ ulogp,
                                                              int32_t* __restrict__ unext) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const long row = i / K;
     if ((int64_t)(row % Tlen) >= in_lens[row / Tlen]) return;  // (no token set was written for this frame)
-    const int e = ng_root_edge(g, tok[i]);
+    const int e = tab_root_edge(g.first, g.tok, tok[i]);
     ulogp[i] = e >= 0 ? g.logp[e] : 0.f;  // (a root without the edge: the caller's tables are broken, the token scores 0)
     unext[i] = e >= 0 ? g.next[e] : 0;
 }
@@ -248,7 +187,7 @@ struct BeamArgs {
 };
 struct BeamArgsBias : BeamArgs {  // contextual biasing: what ctc_beam_kernel<true> takes on top
     const int32_t* rootc;  // [B][T][K]
-    const int32_t *b_first, *b_tok, *b_child, *b_unc;
+    BiasTab bias;  // n_nodes == 0: no list
     float b_weight;
     float* bias_sum;     // [B][nbest]
     int32_t* bias_node;  // [B][nbest]
@@ -256,7 +195,7 @@ struct BeamArgsBias : BeamArgs {  // contextual biasing: what ctc_beam_kernel<tr
 struct BeamArgsNgram : BeamArgsBias {  // n-gram model: what ctc_beam_kernel<*, true> takes on top (the bias fields unused without a list)
     const float* ulogp;    // [B][T][K]
     const int32_t* unext;  // [B][T][K]
-    NgramTabs ng;
+    NgramTab ng;  // n_nodes == 0: no model
     int ng_start, ng_eos;
     float ng_weight, len_bonus;
     float* ngram_sum;     // [B][nbest]
@@ -415,7 +354,7 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
             s_live = 0;
         }
         if constexpr (BIAS)  // what a mismatch at entry i takes back: the one table read of an entry that does not stand at the root
-            for (int i = tid; i < n; i += NT) s_bu[i] = s_bn[cur][i] ? a.b_unc[s_bn[cur][i]] : 0;
+            for (int i = tid; i < n; i += NT) s_bu[i] = s_bn[cur][i] ? a.bias.unc[s_bn[cur][i]] : 0;
         lds_barrier();
         // ---- P2: the candidates.  Slot i * (K + 1) + k: entry i extended by token k (k < K) or staying (k == K)
         int alive = 0;
@@ -445,17 +384,8 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
                     const int sn = s_bn[cur][i], rc = st_root[k];
                     int step = -1;
                     if (sn != 0) {  // rule 1 below the root: binary search among the node's own edges
-                        const int c = st_tok[k];
-                        int lo = a.b_first[sn], hi = a.b_first[sn + 1];
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1, x = a.b_tok[mid];
-                            if (x == c) {
-                                step = a.b_child[mid] | CB_BIAS_PLUS;
-                                break;
-                            }
-                            if (x < c) lo = mid + 1;
-                            else hi = mid;
-                        }
+                        const int e = tab_edge(a.bias.first, a.bias.tok, sn, st_tok[k]);
+                        if (e >= 0) step = a.bias.child[e] | CB_BIAS_PLUS;
                     }
                     if (step < 0) step = (sn != 0 ? CB_BIAS_BACK : 0) | (rc >= 0 ? rc | CB_BIAS_PLUS : 0);  // rule 2 (at the root: rule 1)
                     s_cb[i * K + k] = step;
@@ -611,13 +541,13 @@ __global__ __launch_bounds__(CB_NT_MAX) void ctc_beam_kernel(typename BeamArgsOf
         a.pb[(long)b * nbest + r] = ok ? s_pb[cur][r] : neg_inf();
         a.pnb[(long)b * nbest + r] = ok ? s_pnb[cur][r] : neg_inf();
         if constexpr (BIAS) {  // <eos> is never in the trie: it takes the uncommitted part back
-            a.bias_sum[(long)b * nbest + r] = ok ? (float)(s_bg[cur][r] - a.b_unc[s_bn[cur][r]]) : 0.f;
+            a.bias_sum[(long)b * nbest + r] = ok ? (float)(s_bg[cur][r] - a.bias.unc[s_bn[cur][r]]) : 0.f;
             a.bias_node[(long)b * nbest + r] = ok ? s_bn[cur][r] : 0;
         }
         if constexpr (NGRAM) {  // a finished hypothesis also pays for its </s>
             float G = 0.f;
             if (ok) {
-                const int e = ng_root_edge(a.ng, a.ng_eos);
+                const int e = tab_root_edge(a.ng.first, a.ng.tok, a.ng_eos);
                 int nx;
                 G = __builtin_bit_cast(float, s_ng[cur][r]);
                 G += ng_lookup(a.ng, s_nn[cur][r], a.ng_eos, e >= 0 ? a.ng.logp[e] : 0.f, e >= 0 ? a.ng.next[e] : 0, nx);
@@ -720,26 +650,12 @@ __global__ __launch_bounds__(64) void ctc_score_alpha_kernel(const float* __rest
 
 int64_t align16(int64_t x) { return (x + 15) / 16 * 16; }
 
-struct BiasList {  // what avsr_ctc_beam_search_bias adds to the plain call
-    const int32_t *first, *tok, *child, *unc;
-    float weight;
-    float* sum;
-    int32_t* node;
-};
-
-struct NgramModel {  // what avsr_ctc_beam_search_ngram adds to either
-    NgramTabs tabs;
-    int start, eos;
-    float weight, len_bonus;
-    float* sum;
-    int32_t* node;
-};
-
-__global__ __launch_bounds__(256) void ctc_bias_zero_kernel(float* __restrict__ bias_sum, int32_t* __restrict__ bias_node, int n) {
+// the outputs of a scorer that took no part (no bias list / no n-gram model): sums and nodes of the n-best are zeros
+__global__ __launch_bounds__(256) void ctc_zero_outputs_kernel(float* __restrict__ sum, int32_t* __restrict__ node, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
-        bias_sum[i] = 0.f;
-        bias_node[i] = 0;
+        sum[i] = 0.f;
+        node[i] = 0;
     }
 }
 
@@ -756,11 +672,12 @@ extern "C" int64_t avsr_ctc_beam_workspace_bytes(int B, int T, int W, int K) {
     return beam_rec_offset(B, T, W, K) + (int64_t)B * T * W * 16;
 }
 
-// the plain search (bias == nullptr) or the search with a bias list, whose root-child table follows the plain layout; with an n-gram
-// model (ng != nullptr) the root's (logp, next) tables follow either
+// The search.  `a` arrives with the scorers' part filled in by the entry point (tables, weights, outputs) and everything else zero:
+// a.bias.n_nodes != 0 is the search with a bias list, whose root-child table follows the plain workspace layout; a.ng.n_nodes != 0
+// the search with an n-gram model, whose root (logp, next) tables follow either.
 static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest, int32_t* tokens,
                        int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid, void* workspace, int B, int T, int V,
-                       hipStream_t stream, const BiasList* bias, const NgramModel* ng = nullptr) {
+                       hipStream_t stream, BeamArgsNgram a) {
     AVSR_REQUIRE(W >= 2 && W <= CB_MAXW, "ctc_beam_search: beam must be 2 .. 64");
     AVSR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V - 1, "ctc_beam_search: token budget must be 1 .. min(32, V - 1)");
     AVSR_REQUIRE(nbest >= 1 && nbest <= W, "ctc_beam_search: nbest must be 1 .. beam");
@@ -769,7 +686,7 @@ static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int 
     AVSR_REQUIRE(T >= 1 && (int64_t)T * W < (1 << 30), "ctc_beam_search: 1 .. 2^30 / beam frames");
     AVSR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_beam_search: workspace must be 16-byte aligned");
     if (B <= 0) return 0;
-    BeamArgsNgram a;
+    const bool biased = a.bias.n_nodes != 0, ngram = a.ng.n_nodes != 0;
     int32_t* tok = reinterpret_cast<int32_t*>(workspace);
     float* val = reinterpret_cast<float*>(tok + (int64_t)B * T * K);
     float* blk = val + (int64_t)B * T * K;
@@ -796,49 +713,40 @@ static int beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int 
     int nt = (W * (K + 1) + 63) / 64 * 64 * 4;
     nt = nt < CB_NT_MIN ? CB_NT_MIN : (nt > CB_NT_MAX ? CB_NT_MAX : nt);
     const long total = (long)B * T * K;
-    if (ng != nullptr) {
+    if (ngram) {
         char* after = reinterpret_cast<char*>(workspace) +
-                      (bias ? avsr_ctc_beam_bias_workspace_bytes(B, T, W, K) : avsr_ctc_beam_workspace_bytes(B, T, W, K));
+                      (biased ? avsr_ctc_beam_bias_workspace_bytes(B, T, W, K) : avsr_ctc_beam_workspace_bytes(B, T, W, K));
         float* ulogp = reinterpret_cast<float*>(after);
         int32_t* unext = reinterpret_cast<int32_t*>(after + align16(total * 4));
         a.ulogp = ulogp;
         a.unext = unext;
-        a.ng = ng->tabs;
-        a.ng_start = ng->start;
-        a.ng_eos = ng->eos;
-        a.ng_weight = ng->weight;
-        a.len_bonus = ng->len_bonus;
-        a.ngram_sum = ng->sum;
-        a.ngram_node = ng->node;
         AVSR_LAUNCH(ctc_ngram_root_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tok, in_lens, a.ng, K, T, total, ulogp,
                     unext);
     }
-    if (bias == nullptr) {
-        if (ng == nullptr) AVSR_LAUNCH((ctc_beam_kernel<false, false>), dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgs&>(a));
+    if (!biased) {
+        if (!ngram) AVSR_LAUNCH((ctc_beam_kernel<false, false>), dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgs&>(a));
         else AVSR_LAUNCH((ctc_beam_kernel<false, true>), dim3(B), dim3(nt), 0, stream, a);
     } else {
         int32_t* rootc = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + avsr_ctc_beam_workspace_bytes(B, T, W, K));
         a.rootc = rootc;
-        a.b_first = bias->first;
-        a.b_tok = bias->tok;
-        a.b_child = bias->child;
-        a.b_unc = bias->unc;
-        a.b_weight = bias->weight;
-        a.bias_sum = bias->sum;
-        a.bias_node = bias->node;
-        AVSR_LAUNCH(ctc_root_child_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tok, in_lens, a.b_first, a.b_tok,
-                    a.b_child, K, T, total, rootc);
-        if (ng == nullptr) AVSR_LAUNCH((ctc_beam_kernel<true, false>), dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgsBias&>(a));
+        AVSR_LAUNCH(ctc_root_child_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tok, in_lens, a.bias, K, T, total, rootc);
+        if (!ngram) AVSR_LAUNCH((ctc_beam_kernel<true, false>), dim3(B), dim3(nt), 0, stream, static_cast<const BeamArgsBias&>(a));
         else AVSR_LAUNCH((ctc_beam_kernel<true, true>), dim3(B), dim3(nt), 0, stream, a);
     }
     AVSR_CHECK_LAUNCH("ctc_beam_search");
     return 0;
 }
 
+static int zero_outputs(const char* where, float* sum, int32_t* node, int n, hipStream_t stream) {
+    AVSR_LAUNCH(ctc_zero_outputs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sum, node, n);
+    AVSR_CHECK_LAUNCH(where);
+    return 0;
+}
+
 extern "C" int avsr_ctc_beam_search(const float* lp, int64_t ld, const int64_t* in_lens, int blank, int W, int K, int nbest,
                                     int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb, int32_t* n_valid,
                                     void* workspace, int B, int T, int V, hipStream_t stream) {
-    return beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, nullptr);
+    return beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, BeamArgsNgram{});
 }
 
 extern "C" int64_t avsr_ctc_beam_bias_workspace_bytes(int B, int T, int W, int K) {
@@ -851,19 +759,19 @@ extern "C" int avsr_ctc_beam_search_bias(const float* lp, int64_t ld, const int6
                                          int n_edges, float weight, int32_t* tokens, int32_t* lens, float* score, float* pb, float* pnb,
                                          int32_t* n_valid, float* bias_sum, int32_t* bias_node, void* workspace, int B, int T, int V,
                                          hipStream_t stream) {
-    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_BIAS_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_BIAS_MAX_EDGES,
-                 "ctc_beam_search_bias: too many nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
-    AVSR_REQUIRE(weight == weight && fabsf(weight) <= 1e30f, "ctc_beam_search_bias: the weight must be finite");
-    if (n_nodes == 0 || n_edges == 0) {  // no list: the plain search, and nothing was boosted
-        const int rc = beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream,
-                                   nullptr);
-        if (rc != 0 || B <= 0) return rc;
-        AVSR_LAUNCH(ctc_bias_zero_kernel, dim3((unsigned)((B * nbest + 255) / 256)), dim3(256), 0, stream, bias_sum, bias_node, B * nbest);
-        AVSR_CHECK_LAUNCH("ctc_beam_search_bias");
-        return 0;
+    AVSR_REQUIRE_NONE("ctc_beam_search_bias", bias_sizes_refusal(n_nodes, n_edges));
+    AVSR_REQUIRE_NONE("ctc_beam_search_bias", weight_refusal(weight, WEIGHT_UP_TO_1E30));
+    const bool biased = tables_given(n_nodes, n_edges);
+    BeamArgsNgram a{};
+    if (biased) {
+        a.bias = BiasTab{first, tok, child, unc, n_nodes};
+        a.b_weight = weight;
+        a.bias_sum = bias_sum;
+        a.bias_node = bias_node;
     }
-    const BiasList bias = {first, tok, child, unc, weight, bias_sum, bias_node};
-    return beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, &bias);
+    const int rc = beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, a);
+    if (rc != 0 || B <= 0 || biased) return rc;
+    return zero_outputs("ctc_beam_search_bias", bias_sum, bias_node, B * nbest, stream);  // no list: the plain search, nothing was boosted
 }
 
 extern "C" int64_t avsr_ctc_beam_ngram_workspace_bytes(int B, int T, int W, int K, int with_bias) {
@@ -879,34 +787,39 @@ extern "C" int avsr_ctc_beam_search_ngram(const float* lp, int64_t ld, const int
                                           int start_node, int eos, float ngram_weight, float len_bonus, int32_t* tokens, int32_t* lens,
                                           float* score, float* pb, float* pnb, int32_t* n_valid, float* bias_sum, int32_t* bias_node,
                                           float* ngram_sum, int32_t* ngram_node, void* workspace, int B, int T, int V, hipStream_t stream) {
-    AVSR_REQUIRE(b_nodes >= 0 && b_nodes <= AVSR_BIAS_MAX_NODES && b_edges >= 0 && b_edges <= AVSR_BIAS_MAX_EDGES,
-                 "ctc_beam_search_ngram: too many bias nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
-    AVSR_REQUIRE(bias_weight == bias_weight && fabsf(bias_weight) <= 1e30f, "ctc_beam_search_ngram: the bias weight must be finite");
-    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_NGRAM_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_NGRAM_MAX_EDGES,
-                 "ctc_beam_search_ngram: too many nodes or edges (AVSR_NGRAM_MAX_NODES / AVSR_NGRAM_MAX_EDGES)");
-    AVSR_REQUIRE(ngram_weight == ngram_weight && fabsf(ngram_weight) <= 1e30f && len_bonus == len_bonus && fabsf(len_bonus) <= 1e30f,
+    AVSR_REQUIRE_NONE("ctc_beam_search_ngram", bias_sizes_refusal(b_nodes, b_edges));
+    AVSR_REQUIRE(!weight_refusal(bias_weight, WEIGHT_UP_TO_1E30), "ctc_beam_search_ngram: the bias weight must be finite");
+    AVSR_REQUIRE_NONE("ctc_beam_search_ngram", ngram_sizes_refusal(n_nodes, n_edges));
+    AVSR_REQUIRE(!weight_refusal(ngram_weight, WEIGHT_UP_TO_1E30) && !weight_refusal(len_bonus, WEIGHT_UP_TO_1E30),
                  "ctc_beam_search_ngram: the n-gram weight and the length bonus must be finite");
-    const bool biased = b_nodes != 0 && b_edges != 0;
-    const BiasList bias = {first, tok, child, unc, bias_weight, bias_sum, bias_node};
-    if (n_nodes == 0 || n_edges == 0) {  // no model: the biased or the plain search, and nothing was scored
+    if (!tables_given(n_nodes, n_edges)) {  // no model: the biased or the plain search, and nothing was scored
         const int rc = avsr_ctc_beam_search_bias(lp, ld, in_lens, blank, W, K, nbest, first, tok, child, unc, b_nodes, b_edges, bias_weight,
                                                  tokens, lens, score, pb, pnb, n_valid, bias_sum, bias_node, workspace, B, T, V, stream);
         if (rc != 0 || B <= 0) return rc;
-        AVSR_LAUNCH(ctc_bias_zero_kernel, dim3((unsigned)((B * nbest + 255) / 256)), dim3(256), 0, stream, ngram_sum, ngram_node, B * nbest);
-        AVSR_CHECK_LAUNCH("ctc_beam_search_ngram");
-        return 0;
+        return zero_outputs("ctc_beam_search_ngram", ngram_sum, ngram_node, B * nbest, stream);
     }
     AVSR_REQUIRE(start_node >= 0 && start_node < n_nodes, "ctc_beam_search_ngram: start node outside the model");
     AVSR_REQUIRE(blank == 0, "ctc_beam_search_ngram: the model's tables take the blank to be id 0");
     AVSR_REQUIRE(eos == V - 1, "ctc_beam_search_ngram: </s> must be the last id of the vocabulary");
-    AVSR_REQUIRE(n_first && n_tok && n_logp && n_next && n_bow && n_back, "ctc_beam_search_ngram: missing table");
-    const NgramModel ng = {{n_first, n_tok, n_logp, n_next, n_bow, n_back}, start_node, eos, ngram_weight, len_bonus, ngram_sum, ngram_node};
-    const int rc = beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream,
-                               biased ? &bias : nullptr, &ng);
+    const bool biased = tables_given(b_nodes, b_edges);
+    BeamArgsNgram a{};
+    a.ng = NgramTab{n_first, n_tok, n_logp, n_next, n_bow, n_back, n_nodes};
+    AVSR_REQUIRE_NONE("ctc_beam_search_ngram", missing_table(a.ng));
+    a.ng_start = start_node;
+    a.ng_eos = eos;
+    a.ng_weight = ngram_weight;
+    a.len_bonus = len_bonus;
+    a.ngram_sum = ngram_sum;
+    a.ngram_node = ngram_node;
+    if (biased) {
+        a.bias = BiasTab{first, tok, child, unc, b_nodes};
+        a.b_weight = bias_weight;
+        a.bias_sum = bias_sum;
+        a.bias_node = bias_node;
+    }
+    const int rc = beam_search(lp, ld, in_lens, blank, W, K, nbest, tokens, lens, score, pb, pnb, n_valid, workspace, B, T, V, stream, a);
     if (rc != 0 || B <= 0 || biased) return rc;
-    AVSR_LAUNCH(ctc_bias_zero_kernel, dim3((unsigned)((B * nbest + 255) / 256)), dim3(256), 0, stream, bias_sum, bias_node, B * nbest);
-    AVSR_CHECK_LAUNCH("ctc_beam_search_ngram");
-    return 0;
+    return zero_outputs("ctc_beam_search_ngram", bias_sum, bias_node, B * nbest, stream);
 }
 
 // Workspace layout: lpg[B*N*T*Smax] f32 | ext[B*N*Smax] i32 | lens[B*N] i32

@@ -29,6 +29,7 @@
 
 #include "prims.h"
 #include "avsr_hip.h"
+#include "search_tables.h"
 
 #ifdef AVSR_EMU
 static inline int avsr_copy_to_host_sync(void* dst, const void* src, size_t n, hipStream_t) {
@@ -781,44 +782,6 @@ __global__ __launch_bounds__(SEL_NT) void logsoftmax_prebeam_kernel(const float*
 // term (the partial scorers in their listed order: ctc, ngram), before the hypothesis' score.  ONE block: radix select of the
 // K best values, then a rank sort of those K (value descending, entry ascending).
 // ---------------------------------------------------------------------------------------------------------------------
-// Contextual biasing (auto_avsr_amd/bias.py: ContextBiasScorer): a trie of phrases in CSR form -- node s owns the edges
-// [first[s], first[s + 1]) with tokens tok[] ascending and targets child[] (an end node without children already replaced by the
-// root 0), unc[s] = edges from s up to its nearest end ancestor-or-self (or the root).  A hypothesis carries one node.
-struct BiasTab {
-    const int *first, *tok, *child, *unc;
-    int n_nodes;  // 0: no list
-};
-
-// edge of node s on token v, -1 if there is none: binary search among the node's children
-AVSR_DEV int bias_edge(const BiasTab& t, int s, int v) {
-    int lo = t.first[s], hi = t.first[s + 1];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int x = t.tok[mid];
-        if (x == v) return mid;
-        if (x < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return -1;
-}
-
-// gain of extending a hypothesis at node s by token v and the node it reaches: +1 along an edge; otherwise the uncommitted reward of
-// s is taken back and v alone is retried from the root (no failure links)
-AVSR_DEV int bias_gain(const BiasTab& t, int s, int v, int& next) {
-    int e = bias_edge(t, s, v);
-    if (e >= 0) {
-        next = t.child[e];
-        return 1;
-    }
-    int g = -t.unc[s];
-    next = 0;
-    if (s != 0 && (e = bias_edge(t, 0, v)) >= 0) {
-        next = t.child[e];
-        g += 1;
-    }
-    return g;
-}
-
 // the lookup on its own (avsr_bias_score): entry (row, c) of gain / next [n][S + 1], column S = <eos>
 __global__ __launch_bounds__(256) void bias_score_kernel(BiasTab t, const int* __restrict__ node, const int64_t* __restrict__ cand, int n, int S,
                                                          int eos, float* __restrict__ gain, int* __restrict__ next) {
@@ -829,63 +792,6 @@ __global__ __launch_bounds__(256) void bias_score_kernel(BiasTab t, const int* _
     if (t.n_nodes > 0) g = bias_gain(t, node[row], c < S ? (int)cand[(size_t)row * S + c] : eos, nx);
     gain[i] = (float)g;
     next[i] = nx;
-}
-
-// Back-off n-gram language model (auto_avsr_amd/ngram.py: NgramScorer), a PARTIAL scorer: a node is a context (an n-gram of order
-// < N, node 0 the empty one) that owns the edges [first[s], first[s + 1]) with tokens tok[] ascending, log-probabilities logp[] and
-// next[] = the node of the extended context; bow[s] is the node's back-off weight, back[s] the node of its longest proper suffix
-// that is a node.  A hypothesis carries one node.
-struct NgramTab {
-    const int *first, *tok;
-    const float* logp;
-    const int* next;
-    const float* bow;
-    const int* back;
-    int n_nodes;  // 0: no model
-};
-
-// edge of node s on token v, -1 if there is none.  The root of NgramScorer's tables holds the tokens 1 .. V - 1 in order, so its edge
-// on v is tried at its place first: one load instead of a 13-step search at the node every back-off chain ends at.
-AVSR_DEV int ngram_edge(const NgramTab& t, int s, int v) {
-    int lo = t.first[s], hi = t.first[s + 1];
-    if (s == 0) {
-        const int g = lo + v - 1;
-        if (g >= lo && g < hi && t.tok[g] == v) return g;
-    }
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int x = t.tok[mid];
-        if (x == v) return mid;
-        if (x < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return -1;
-}
-
-// log p(v | node s) by ARPA back-off and the node reached: walk s, back[s], ... to the first node with an edge e on v; logp[e] if
-// that is s itself, else r = bow[s0]; r += bow[s1]; ...; r += logp[e] (f32, this order: ngram.py's host lookup adds alike).  The
-// blank scores 0 and keeps the node.  The walk is cut after AVSR_NGRAM_MAX_ORDER hops (tables are not validated: a cycle in back[]
-// must not hang the step); a token without an edge at the root gets the back-offs alone.
-AVSR_DEV float ngram_logp(const NgramTab& t, int s, int v, int blank, int& next) {
-    next = s;
-    if (v == blank) return 0.f;
-    int e = ngram_edge(t, s, v);
-    if (e >= 0) {
-        next = t.next[e];
-        return t.logp[e];
-    }
-    float r = t.bow[s];
-    for (int hop = 0; s != 0 && hop < AVSR_NGRAM_MAX_ORDER; hop++) {
-        s = t.back[s];
-        e = ngram_edge(t, s, v);
-        if (e >= 0) {
-            next = t.next[e];
-            return r + t.logp[e];
-        }
-        r += t.bow[s];
-    }
-    next = 0;
-    return r;
 }
 
 // the lookup on its own (avsr_ngram_score): entry (row, c) of score / next [n][S + 1], column S = <eos>
@@ -1559,13 +1465,12 @@ extern "C" int avsr_beam_attach_lm(int64_t h, const int32_t* cfg, const float* f
 
 // The trie lookup of contextual biasing on its own (tests, the python-issued step's cross-check): row r stands at node[r]; entry
 // (r, c) of gain / next [n][S + 1] is the gain of extending it by cand[r][c] (c < S) or by <eos> (c = S) and the node reached.
-// n_nodes == 0 (no list): zeros.  The tables are device memory in the layout of `struct BiasTab`; they are not validated.
+// n_nodes == 0 (no list): zeros.  The tables are device memory in the layout of `struct BiasTab` (search_tables.h); they are not validated.
 extern "C" int avsr_bias_score(const int32_t* first, const int32_t* tok, const int32_t* child, const int32_t* unc, int n_nodes, int n_edges,
                                const int32_t* node, const int64_t* cand, int n, int S, int eos, float* gain, int32_t* next, hipStream_t stream) {
-    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_BIAS_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_BIAS_MAX_EDGES,
-                 "bias_score: too many nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
+    AVSR_REQUIRE_NONE("bias_score", bias_sizes_refusal(n_nodes, n_edges));
     AVSR_REQUIRE(n >= 1 && S >= 0 && (int64_t)n * (S + 1) <= ((int64_t)1 << 30), "bias_score: bad sizes");
-    const BiasTab t{first, tok, child, unc, n_edges > 0 ? n_nodes : 0};
+    const BiasTab t{first, tok, child, unc, tables_given(n_nodes, n_edges) ? n_nodes : 0};
     const long total = (long)n * (S + 1);
     AVSR_LAUNCH(bias_score_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, t, node, cand, n, S, eos, gain, next);
     AVSR_CHECK_LAUNCH("bias_score");
@@ -1581,13 +1486,12 @@ extern "C" int avsr_beam_set_bias(int64_t h, const int32_t* cfg, const float* fc
     Session* sp = reinterpret_cast<Session*>((intptr_t)h);
     AVSR_REQUIRE(sp != nullptr, "beam_set_bias: no session");
     const int n_nodes = cfg[0], n_edges = cfg[1];
-    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_BIAS_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_BIAS_MAX_EDGES,
-                 "beam_set_bias: too many nodes or edges (AVSR_BIAS_MAX_NODES / AVSR_BIAS_MAX_EDGES)");
+    AVSR_REQUIRE_NONE("beam_set_bias", bias_sizes_refusal(n_nodes, n_edges));
     Bias b;
-    if (n_nodes > 0 && n_edges > 0) {
-        AVSR_REQUIRE(first && tok && child && unc, "beam_set_bias: missing table");
-        AVSR_REQUIRE(fcfg[0] == fcfg[0], "beam_set_bias: the weight is not a number");
+    if (tables_given(n_nodes, n_edges)) {
         b.tab = BiasTab{first, tok, child, unc, n_nodes};
+        AVSR_REQUIRE_NONE("beam_set_bias", missing_table(b.tab));
+        AVSR_REQUIRE_NONE("beam_set_bias", weight_refusal(fcfg[0], WEIGHT_NOT_NAN));
         b.w = fcfg[0];
     }
     sp->bias_next = b;
@@ -1596,15 +1500,14 @@ extern "C" int avsr_beam_set_bias(int64_t h, const int32_t* cfg, const float* fc
 
 // The n-gram lookup on its own (tests, the python-issued step's cross-check): row r stands at node[r]; entry (r, c) of score / next
 // [n][S + 1] is log p of extending it by cand[r][c] (c < S) or by <eos> (c = S) and the node reached; the blank scores 0 and keeps
-// the node.  n_nodes == 0 (no model): zeros.  The tables are device memory in the layout of `struct NgramTab`; they are not validated.
+// the node.  n_nodes == 0 (no model): zeros.  The tables are device memory in the layout of `struct NgramTab` (search_tables.h); they are not validated.
 extern "C" int avsr_ngram_score(const int32_t* first, const int32_t* tok, const float* logp, const int32_t* next_tab, const float* bow,
                                 const int32_t* back, int n_nodes, int n_edges, const int32_t* node, const int64_t* cand, int n, int S, int eos,
                                 int blank, float* score, int32_t* next, hipStream_t stream) {
-    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_NGRAM_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_NGRAM_MAX_EDGES,
-                 "ngram_score: too many nodes or edges (AVSR_NGRAM_MAX_NODES / AVSR_NGRAM_MAX_EDGES)");
+    AVSR_REQUIRE_NONE("ngram_score", ngram_sizes_refusal(n_nodes, n_edges));
     AVSR_REQUIRE(n >= 1 && S >= 0 && (int64_t)n * (S + 1) <= ((int64_t)1 << 30), "ngram_score: bad sizes");
-    const NgramTab t{first, tok, logp, next_tab, bow, back, n_edges > 0 ? n_nodes : 0};
-    AVSR_REQUIRE(t.n_nodes == 0 || (first && tok && logp && next_tab && bow && back), "ngram_score: missing table");
+    const NgramTab t{first, tok, logp, next_tab, bow, back, tables_given(n_nodes, n_edges) ? n_nodes : 0};
+    if (t.n_nodes != 0) AVSR_REQUIRE_NONE("ngram_score", missing_table(t));
     const long total = (long)n * (S + 1);
     AVSR_LAUNCH(ngram_score_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, t, node, cand, n, S, eos, blank, score, next);
     AVSR_CHECK_LAUNCH("ngram_score");
@@ -1621,16 +1524,15 @@ extern "C" int avsr_beam_set_ngram(int64_t h, const int32_t* cfg, const float* f
     Session* sp = reinterpret_cast<Session*>((intptr_t)h);
     AVSR_REQUIRE(sp != nullptr, "beam_set_ngram: no session");
     const int n_nodes = cfg[0], n_edges = cfg[1], start = cfg[2];
-    AVSR_REQUIRE(n_nodes >= 0 && n_nodes <= AVSR_NGRAM_MAX_NODES && n_edges >= 0 && n_edges <= AVSR_NGRAM_MAX_EDGES,
-                 "beam_set_ngram: too many nodes or edges (AVSR_NGRAM_MAX_NODES / AVSR_NGRAM_MAX_EDGES)");
+    AVSR_REQUIRE_NONE("beam_set_ngram", ngram_sizes_refusal(n_nodes, n_edges));
     Ngram m;
-    if (n_nodes > 0 && n_edges > 0) {
-        AVSR_REQUIRE(first && tok && logp && next_tab && bow && back, "beam_set_ngram: missing table");
+    if (tables_given(n_nodes, n_edges)) {
+        m.tab = NgramTab{first, tok, logp, next_tab, bow, back, n_nodes};
+        AVSR_REQUIRE_NONE("beam_set_ngram", missing_table(m.tab));
         AVSR_REQUIRE(start >= 0 && start < n_nodes, "beam_set_ngram: the start node is not a node");
-        AVSR_REQUIRE(fcfg[0] - fcfg[0] == 0.f, "beam_set_ngram: the weight is not a finite number");
+        AVSR_REQUIRE_NONE("beam_set_ngram", weight_refusal(fcfg[0], WEIGHT_FINITE));
         if (!sp->ng_host) sp->ng_host = avsr_host_floats(MAX_ROWS);
         AVSR_REQUIRE(sp->ng_host != nullptr, "beam_set_ngram: no host memory for the running sums");
-        m.tab = NgramTab{first, tok, logp, next_tab, bow, back, n_nodes};
         m.start = start;
         m.w = fcfg[0];
     }

@@ -8,6 +8,7 @@ decoder pass on the new position over cached K / V, pre-beam, CTC prefix scores,
 of U utterances whose running hypotheses share every step; `search` is the group of one.  The loop only looks at the 1 KB per
 utterance the step copies back (tokens, parents, scores), collects ended hypotheses and applies the end-detection rule.  Any
 other scorer configuration keeps the python step of decoding.py."""
+import collections
 import contextlib
 import ctypes
 import math
@@ -29,6 +30,15 @@ def search_maxlen(T, maxlenratio):
     if maxlenratio < 0:
         return -1 * int(maxlenratio)
     return max(1, int(maxlenratio * T))
+
+
+# A scorer whose device tables a session takes (NativeBeam._bind_tables): the dict of the search that holds it, the entry point that
+# binds its tables, cfg of a scorer as that entry point reads it (fcfg is the weight alone), the cfg that detaches, the number of tables
+_TableScorer = collections.namedtuple("_TableScorer", "scorers entry cfg cfg_detached n_tables")
+_TABLE_SCORERS = {
+    "bias": _TableScorer("full_scorers", "avsr_beam_set_bias", lambda sc: (sc.n_nodes if sc.n_edges else 0, sc.n_edges), (0, 0), 4),
+    "ngram": _TableScorer("part_scorers", "avsr_beam_set_ngram", lambda sc: (sc.n_nodes, sc.n_edges, sc.start_node), (0, 0, 0), 6),
+}
 
 
 def skinny_len_ok(K, sliced_ok):
@@ -54,6 +64,7 @@ class NativeBeam:
         self.lib = None  # the library object that made `handle` (a session is destroyed by the library that created it)
         self.key = None
         self.keep_alive = []
+        self.bias_key = self.bias_keep = self.ngram_key = self.ngram_keep = None  # what _bind_tables sent to the session
 
     def __del__(self):
         try:
@@ -134,8 +145,8 @@ class NativeBeam:
         if lm is not None:
             key += (lm_pe.data_ptr(), lm_pe.shape[0], float(bs.weights["lm"]))
         if key == self.key:
-            self._bind_bias(dev)
-            self._bind_ngram(dev)
+            for kind in _TABLE_SCORERS:
+                self._bind_tables(kind, dev)
             return
         L = _lib.lib()
         if self.handle:
@@ -192,50 +203,31 @@ class NativeBeam:
         self.handle, self.lib, self.key, self.keep_alive = h, L, key, keep
         self.V, self.pe_rows = V, pe.shape[0]
         self.group_host = self.group_yseq_host = None  # pinned result buffers of search_group, sized by the largest group so far
-        self.bias_key = None
-        self._bind_bias(dev)
-        self.ngram_key = None
-        self._bind_ngram(dev)
+        for kind in _TABLE_SCORERS:  # (a new session has nothing bound)
+            setattr(self, kind + "_key", None)
+            self._bind_tables(kind, dev)
 
-    def _bind_ngram(self, dev):
-        """The model of scorers["ngram"] (avsr_beam_set_ngram), on the terms of `_bind_bias`: re-sent when the model's version or its
-        weight changed, or the session is new; detached when the scorer left the search."""
-        sc = self.bs.part_scorers.get("ngram")
+    def _bind_tables(self, kind, dev):
+        """The device tables of scorers[kind] -- the bias list (avsr_beam_set_bias) or the n-gram model (avsr_beam_set_ngram): re-sent
+        when the scorer's version or its weight changed, or the session is new -- never a reason to rebuild the session; detached when
+        the scorer left the search after its tables were bound.  Takes effect at the next avsr_beam_begin / _begin_batch."""
+        kd = _TABLE_SCORERS[kind]
+        sc = getattr(self.bs, kd.scorers).get(kind)
+        bound = getattr(self, kind + "_key")
+        if sc is None:
+            if bound is None:
+                return
+            key, tabs, cfg, weight, ptrs = None, None, kd.cfg_detached, 0.0, [None] * kd.n_tables
+        else:
+            key = (id(sc), sc.version, float(self.bs.weights[kind]), str(dev))
+            if key == bound:
+                return
+            tabs = sc.device_tables(dev)
+            cfg, weight, ptrs = kd.cfg(sc), self.bs.weights[kind], [t.data_ptr() for t in tabs]
         vp = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
-        if sc is None:
-            if getattr(self, "ngram_key", None) is not None:
-                self.lib.call("avsr_beam_set_ngram", self.handle, vp((ctypes.c_int32 * 3)(0, 0, 0)), vp((ctypes.c_float * 1)(0.0)),
-                              None, None, None, None, None, None)
-                self.ngram_key, self.ngram_keep = None, None
-            return
-        key = (id(sc), sc.version, float(self.bs.weights["ngram"]), str(dev))
-        if key == self.ngram_key:
-            return
-        tabs = sc.device_tables(dev)
-        self.lib.call("avsr_beam_set_ngram", self.handle, vp((ctypes.c_int32 * 3)(sc.n_nodes, sc.n_edges, sc.start_node)),
-                      vp((ctypes.c_float * 1)(self.bs.weights["ngram"])), *[t.data_ptr() for t in tabs])
-        self.ngram_key, self.ngram_keep = key, tabs  # (the tables stay alive as long as the session may read them)
-
-    def _bind_bias(self, dev):
-        """The bias list of scorers["bias"] (avsr_beam_set_bias): re-sent when the list's version or its weight changed, or the
-        session is new -- never a reason to rebuild the session.  Takes effect at the next avsr_beam_begin / _begin_batch."""
-        sc = self.bs.full_scorers.get("bias")
-        if sc is None:
-            if getattr(self, "bias_key", None) is not None:  # the scorer left the search after a list was bound: detach it
-                cfg, fcfg = (ctypes.c_int32 * 2)(0, 0), (ctypes.c_float * 1)(0.0)
-                self.lib.call("avsr_beam_set_bias", self.handle, ctypes.cast(cfg, ctypes.c_void_p), ctypes.cast(fcfg, ctypes.c_void_p),
-                              None, None, None, None)
-                self.bias_key, self.bias_keep = None, None
-            return
-        key = (id(sc), sc.version, float(self.bs.weights["bias"]), str(dev))
-        if key == self.bias_key:
-            return
-        tabs = sc.device_tables(dev)
-        cfg = (ctypes.c_int32 * 2)(sc.n_nodes if sc.n_edges else 0, sc.n_edges)
-        fcfg = (ctypes.c_float * 1)(self.bs.weights["bias"])
-        self.lib.call("avsr_beam_set_bias", self.handle, ctypes.cast(cfg, ctypes.c_void_p), ctypes.cast(fcfg, ctypes.c_void_p),
-                      *[t.data_ptr() for t in tabs])
-        self.bias_key, self.bias_keep = key, tabs  # (the tables stay alive as long as the session may read them)
+        self.lib.call(kd.entry, self.handle, vp((ctypes.c_int32 * len(cfg))(*cfg)), vp((ctypes.c_float * 1)(weight)), *ptrs)
+        setattr(self, kind + "_key", key)
+        setattr(self, kind + "_keep", tabs)  # (the tables stay alive as long as the session may read them)
 
     @staticmethod
     def _lm_weights(lm, lm_pe):
@@ -406,8 +398,7 @@ def search_many(bs, xs, workers=4, maxlenratio=0.0, minlenratio=0.0):
     cuda = dev.type == "cuda"
     ctc = bs.part_scorers["ctc"]
     pre = [prepare_ctc(ctc, x) for x in xs]
-    maxpos = max((x.shape[0] if maxlenratio == 0 else (-int(maxlenratio) if maxlenratio < 0 else max(1, int(maxlenratio * x.shape[0]))))
-                 for x in xs) + 2
+    maxpos = max(search_maxlen(int(x.shape[0]), maxlenratio) for x in xs) + 2
     workers = max(1, min(workers, len(xs)))
     pool = getattr(bs, "_native_pool", None)
     if pool is None or len(pool) < workers:

@@ -645,6 +645,8 @@ def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=N
             raise ValueError("ctc_beam_search: the n-gram model's tables take the blank to be id 0")
         if not (math.isfinite(float(ngram_weight)) and math.isfinite(float(len_bonus))):
             raise ValueError("ctc_beam_search: ngram_weight and len_bonus must be finite")
+    if biased and bias.n_vocab != V:
+        raise ValueError(f"ctc_beam_search: the bias scorer's vocabulary ({bias.n_vocab}) is not the posteriors' ({V})")
     if fused:
         ws_bytes = call("avsr_ctc_beam_ngram_workspace_bytes", B, T, W, K, int(biased))
     else:
@@ -654,12 +656,13 @@ def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=N
     lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
     n_valid = torch.empty(B, dtype=torch.int32, device=dev)
     score, pb, pnb = (torch.empty(B, nbest, dtype=torch.float32, device=dev) for _ in range(3))
-    if biased and bias.n_vocab != V:
-        raise ValueError(f"ctc_beam_search: the bias scorer's vocabulary ({bias.n_vocab}) is not the posteriors' ({V})")
-    ngram_sum, ngram_node = _zeros_view((B, nbest), torch.float32, dev), _zeros_view((B, nbest), torch.int32, dev)
+
+    def scorer_out(dtype, written):  # an output of a scorer: what the search writes, or read-only zeros where the scorer takes no part
+        return torch.empty(B, nbest, dtype=dtype, device=dev) if written else _zeros_view((B, nbest), dtype, dev)
+
+    bias_sum, bias_node = scorer_out(torch.float32, biased or fused), scorer_out(torch.int32, biased or fused)
+    ngram_sum, ngram_node = scorer_out(torch.float32, fused), scorer_out(torch.int32, fused)
     if fused:
-        bias_sum, ngram_sum = (torch.empty(B, nbest, dtype=torch.float32, device=dev) for _ in range(2))
-        bias_node, ngram_node = (torch.empty(B, nbest, dtype=torch.int32, device=dev) for _ in range(2))
         btabs = bias.device_tables(dev) if biased else (None,) * 4
         ntabs = ngram.device_tables(dev)  # (the scorers keep them alive)
         call("avsr_ctc_beam_search_ngram", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, *[_ptr(t) for t in btabs],
@@ -668,14 +671,11 @@ def ctc_beam_search(lp, ld, in_lens, B, T, V, blank=0, beam=16, topk=16, nbest=N
              _ptr(tokens), _ptr(lens), _ptr(score), _ptr(pb), _ptr(pnb), _ptr(n_valid), _ptr(bias_sum), _ptr(bias_node), _ptr(ngram_sum),
              _ptr(ngram_node), _ptr(ws), B, T, V, _stream(lp))
     elif biased:
-        bias_sum = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-        bias_node = torch.empty(B, nbest, dtype=torch.int32, device=dev)
         tabs = bias.device_tables(dev)  # (the scorer keeps them alive)
         call("avsr_ctc_beam_search_bias", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, *[_ptr(t) for t in tabs],
              bias.n_nodes, bias.n_edges, float(bias_weight), _ptr(tokens), _ptr(lens), _ptr(score), _ptr(pb), _ptr(pnb), _ptr(n_valid),
              _ptr(bias_sum), _ptr(bias_node), _ptr(ws), B, T, V, _stream(lp))
     else:
-        bias_sum, bias_node = _zeros_view((B, nbest), torch.float32, dev), _zeros_view((B, nbest), torch.int32, dev)
         call("avsr_ctc_beam_search", _ptr(lp), ld, _ptr(in_lens), int(blank), W, K, nbest, _ptr(tokens), _ptr(lens), _ptr(score),
              _ptr(pb), _ptr(pnb), _ptr(n_valid), _ptr(ws), B, T, V, _stream(lp))
     out = {"tokens": tokens, "lens": lens, "score": score, "pb": pb, "pnb": pnb, "n_valid": n_valid, "beam": W, "topk": K,

@@ -633,7 +633,9 @@ int avsr_beam_attach_lm(int64_t handle, const int32_t* cfg, const float* fcfg, c
  * -unc[s], and v alone is retried from the root (+1 and that child, or the root): there are no failure links.  The library checks
  * the table SIZES only: the caller is responsible for the contents (first[] ascending with first[0] = 0 and first[n_nodes] =
  * n_edges, every child < n_nodes, tok ascending within a node); tables that break this are read out of bounds inside the step.
- * auto_avsr_amd/bias.py (ContextBiasScorer) builds them and is the one producer in this repository.  Bounds on the table sizes: */
+ * auto_avsr_amd/bias.py (ContextBiasScorer) builds them and is the one producer in this repository; struct BiasTab in
+ * auto_avsr_amd/csrc/search_tables.h is the one reader's view of them, for this call and for avsr_ctc_beam_search_bias.  Bounds on
+ * the table sizes: */
 #define AVSR_BIAS_MAX_NODES (1 << 24)
 #define AVSR_BIAS_MAX_EDGES (1 << 24)
 /* the lookup on its own: row r stands at node[r]; entry (r, c) of gain / next [n][S + 1] = gain and node reached on cand[r][c]
@@ -659,7 +661,8 @@ int avsr_beam_set_bias(int64_t handle, const int32_t* cfg, const float* fcfg, co
  * scores 0 and keeps the node.  The library checks the table SIZES, the start node's range and a finite weight only: the caller is
  * responsible for the contents (first[] as for the bias tables, every next / back < n_nodes, back[] leading to node 0 within
  * AVSR_NGRAM_MAX_ORDER hops -- the walk is cut there --, an edge on every token of the vocabulary but the blank at node 0).
- * auto_avsr_amd/ngram.py (NgramScorer) builds them and is the one producer in this repository.  Bounds: */
+ * auto_avsr_amd/ngram.py (NgramScorer) builds them and is the one producer in this repository; struct NgramTab in
+ * auto_avsr_amd/csrc/search_tables.h is the one reader's view of them, for this call and for avsr_ctc_beam_search_ngram.  Bounds: */
 #define AVSR_NGRAM_MAX_NODES (1 << 26)
 #define AVSR_NGRAM_MAX_EDGES (1 << 27)
 #define AVSR_NGRAM_MAX_ORDER 16
