@@ -90,6 +90,61 @@ __global__ __launch_bounds__(256) void multi_copy_scale_kernel(const OptEntry* _
     }
 }
 
+// Gradient accumulation over a window of micro-steps: acc_i (op)= g_i for every table entry {p = accumulator slice, g = this
+// micro-step's gradient, numel, blk0} (m, v unused), block mapping as above.  window = {micro-steps so far in this window, sum of
+// their batch sizes}, device-resident and only READ here -- grad_window_advance_kernel, launched behind this kernel on the same
+// stream, moves it, so no block can see a half-advanced record.  Position 0 of a window (window[0] == 0) OVERWRITES the
+// accumulator without reading it (nothing to clear beforehand, and a NaN left there does not survive); later micro-steps add;
+// a closing one (close != 0) adds and multiplies by 1 / (sum of batch sizes incl. this one's, or total[0] when given: the sum
+// over all data-parallel ranks) in the same pass.  "First or not" comes from the device record, never from an argument: one
+// captured launch is right wherever in a window it is replayed.  12 B per element (8 at position 0).
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const OptEntry* __restrict__ table, int n,
+                                                              const float* __restrict__ window, float batch, int close,
+                                                              const float* __restrict__ total) {
+    const OptEntry e = find_entry(table, n, blockIdx.x);
+    const long base = (long)(blockIdx.x - e.blk0) * OPT_CHUNK;
+    const bool first = window[0] == 0.f;
+    const float scale = close ? 1.f / (total ? total[0] : window[1] + batch) : 1.f;
+    const bool vec = (((uintptr_t)e.p | (uintptr_t)e.g) & 15) == 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const long i = base + (threadIdx.x + 256 * j) * 4;
+        if (i >= e.numel) break;
+        if (vec && i + 4 <= e.numel) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(e.g + i);
+            if (!first) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(e.p + i);
+#pragma unroll
+                for (int k = 0; k < 4; k++) v[k] = a[k] + v[k];
+            }
+            if (close) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) v[k] *= scale;
+            }
+            *reinterpret_cast<f32x4*>(e.p + i) = v;
+        } else {
+            for (int k = 0; k < 4 && i + k < e.numel; k++) {
+                float v = e.g[i + k];
+                if (!first) v = e.p[i + k] + v;
+                if (close) v *= scale;
+                e.p[i + k] = v;
+            }
+        }
+    }
+}
+
+// one thread, behind grad_accumulate_kernel: an open micro-step counts itself into the window, a closing one empties it
+__global__ __launch_bounds__(64) void grad_window_advance_kernel(float* __restrict__ window, float batch, int close) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (close) {
+        window[0] = 0.f;
+        window[1] = 0.f;
+    } else {
+        window[0] += 1.f;
+        window[1] += batch;
+    }
+}
+
 // partial[block] = sum of squares of the block's chunk of gradients
 __global__ __launch_bounds__(256) void multi_sumsq_kernel(const OptEntry* __restrict__ table, int n, float* __restrict__ partial) {
     __shared__ float red[4];
@@ -390,5 +445,22 @@ extern "C" int avsr_multi_copy_scale(const void* table, int n, int total_blocks,
     if (n <= 0 || total_blocks <= 0) return 0;
     AVSR_LAUNCH(multi_copy_scale_kernel, dim3(total_blocks), dim3(256), 0, stream, reinterpret_cast<const OptEntry*>(table), n, scale);
     AVSR_CHECK_LAUNCH("multi_copy_scale");
+    return 0;
+}
+
+// One micro-step of gradient accumulation for n tensors: ONE multi-tensor launch + a one-thread launch that moves the window.
+// table: entries in the layout of avsr_adamw_step with p = accumulator slice, g = this micro-step's gradient ({acc, g, -, -,
+// numel, blk0}).  window: 2 device floats {micro-steps so far in this window, sum of their batch sizes}, both 0 at the start of
+// a window.  window[0] == 0: acc = g, else acc += g; close != 0: additionally acc *= 1 / (window[1] + batch_size) -- or
+// 1 / total[0] when total (a device float: the sum over every rank's window) is given -- and the window returns to {0, 0};
+// close == 0: the window becomes {window[0] + 1, window[1] + batch_size}.
+extern "C" int avsr_grad_accumulate(const void* table, int n, int total_blocks, float* window, float batch_size, int close,
+                                    const float* total, hipStream_t stream) {
+    AVSR_REQUIRE(table && window && n > 0 && total_blocks > 0, "grad_accumulate: bad arguments");
+    AVSR_REQUIRE(batch_size > 0.f, "grad_accumulate: batch_size must be positive");
+    AVSR_LAUNCH(grad_accumulate_kernel, dim3(total_blocks), dim3(256), 0, stream, reinterpret_cast<const OptEntry*>(table), n,
+                (const float*)window, batch_size, close, total);
+    AVSR_LAUNCH(grad_window_advance_kernel, dim3(1), dim3(64), 0, stream, window, batch_size, close);
+    AVSR_CHECK_LAUNCH("grad_accumulate");
     return 0;
 }

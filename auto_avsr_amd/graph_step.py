@@ -36,7 +36,7 @@ def capture_token():
 
 class StepGraphs:
     def __init__(self, eager_step, *, enabled=True, capture_after=1, max_graphs=64, thread_local=False, warm=None, on_fail=None,
-                 evict=False, on_evict=None):
+                 evict=False, on_evict=None, tag=None):
         """eager_step(x, lens, y) -> tuple of device tensors: the WHOLE step (x: a tensor, or a tuple of tensors -- the
         audio-visual step's (video, audio) -- whose shapes and dtypes all enter the shape key).  It must START by dropping the parameters' gradient
         tensors (`p.grad = None`): the gradients a replay leaves behind live in the graph's memory pool, and an eager step (or a
@@ -45,8 +45,10 @@ class StepGraphs:
         thread_local: capture mode for processes whose other threads touch the device (a process group's watchdog).
         on_fail(exc): called when a capture fails; the step then runs eagerly from there on (None: re-raise).
         evict: drop the least recently used graph beyond max_graphs (default: keep the first max_graphs shapes, run the rest
-        eagerly); on_evict(key): called for every dropped graph."""
-        self.eager_step, self.enabled = eager_step, enabled
+        eagerly); on_evict(key): called for every dropped graph.
+        tag: set when several StepGraphs capture the same shapes next to each other (train_native: the open and the closing
+        micro-step of gradient accumulation); capture_token() and on_evict() then speak of (tag, key) instead of key."""
+        self.eager_step, self.enabled, self.tag = eager_step, enabled, tag
         self.evict, self.on_evict = evict, on_evict
         self.capture_after, self.max_graphs, self.thread_local = capture_after, max_graphs, thread_local
         self.warm, self.on_fail = warm, on_fail
@@ -55,12 +57,15 @@ class StepGraphs:
         self.pool = None
         self.stats = {"eager": 0, "captured": 0, "replayed": 0, "evicted": 0, "full": 0}
 
+    def _token(self, key):
+        return key if self.tag is None else (self.tag, key)
+
     def reset(self):
         """Drop every captured graph (a change of numerical mode, of the optimizer, of the model).  The shared memory pool goes
         with them: a pool handle whose last graph is gone must not be handed to a new capture."""
         if self.on_evict is not None:
             for k in list(self.graphs):
-                self.on_evict(k)
+                self.on_evict(self._token(k))
         self.graphs.clear()
         self.seen.clear()
         self.pool = None
@@ -86,7 +91,7 @@ class StepGraphs:
         g = torch.cuda.CUDAGraph()
         kw = {"capture_error_mode": "thread_local"} if self.thread_local else {}
         global _capture_token
-        _capture_token = key
+        _capture_token = self._token(key)
         try:
             with torch.cuda.graph(g, pool=self.pool, **kw):
                 outs = self.eager_step(sx, sl, sy)
@@ -99,7 +104,7 @@ class StepGraphs:
             old, _ = self.graphs.popitem(last=False)  # (never the one just captured: max_graphs >= 1)
             self.stats["evicted"] += 1
             if self.on_evict is not None:
-                self.on_evict(old)
+                self.on_evict(self._token(old))
 
     def __call__(self, x, lens, y):
         """Run one step on (x, lens, y); returns the step's outputs (static tensors of the graph when replayed: read or copy
@@ -126,7 +131,7 @@ class StepGraphs:
                 self.on_fail(e)
                 self.enabled = False
                 if self.on_evict is not None:
-                    self.on_evict(key)  # whatever the half-finished capture took
+                    self.on_evict(self._token(key))  # whatever the half-finished capture took
                 torch.cuda.synchronize()
                 self.stats["eager"] += 1
                 return self.eager_step(x, lens, y)

@@ -6,7 +6,11 @@ device -- no host synchronisation, capturable in a hipGraph.
 
 cast_weights=True additionally rewrites the bf16 operand copies of the Linear weights (functional.py weight cache) inside
 the update pass (avsr_adamw_cast_step): the step then leaves the model ready for the next forward pass, and the separate
-re-cast launch -- a second read of every f32 weight -- disappears from the training step."""
+re-cast launch -- a second read of every f32 weight -- disappears from the training step.
+
+GradAccumulator: gradient accumulation over a window of micro-steps (Trainer(accumulate_grad_batches=K)) as one more
+multi-tensor launch (avsr_grad_accumulate) into persistent buffers the optimizer then reads; the window's bookkeeping lives on
+the device, so the launch is capturable at one position of a window and valid at any other."""
 import numpy as np
 import torch
 
@@ -15,7 +19,69 @@ from . import ops
 _CHUNK = 4096
 
 
-class FusedAdamW:
+class _PinnedTables:
+    """Pointer tables keyed by gradient addresses, shared by FusedAdamW and GradAccumulator.  Gradients are fresh tensors after
+    every backward pass, so a table is (re)built whenever an unseen set of addresses shows up: written into a pinned host buffer
+    and sent to its device copy on every use (under hipGraph capture that copy becomes a node reading THIS pinned buffer).
+    hipHostMalloc is not allowed while a stream is capturing, so every pinned buffer is allocated up front: each capture keeps one
+    for good -- handed back by release_captured(token) -- and eager steps rotate through the rest."""
+
+    def _init_tables(self, table_bytes, count, slab=False):
+        """slab: the `count` buffers are slices of ONE pinned allocation (many small tables: one hipHostMalloc instead of `count`)"""
+        self._table_bytes = int(table_bytes)
+        self._tables = {}  # gradient addresses -> (pinned host table, device table, n, blocks, scratch, made under capture, token)
+        if slab:
+            one = torch.empty(count * self._table_bytes, dtype=torch.uint8)
+            one = one.pin_memory() if self.device.type == "cuda" else one
+            self._free_host = list(one.split(self._table_bytes))
+        else:
+            self._free_host = [self._new_host() for _ in range(count)]
+
+    def _new_host(self):
+        t = torch.empty(self._table_bytes, dtype=torch.uint8)
+        return t.pin_memory() if self.device.type == "cuda" else t
+
+    def _lookup_table(self, key, build, n, blk):
+        """(device table, n, blk, scratch of blk floats) for `key`; build() -> the table's bytes (a uint8 array) when it is new."""
+        from .graph_step import capture_token
+
+        capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            # a captured step never shares a table with an eager step, even at equal gradient addresses (data-parallel bucket
+            # views and the accumulator's views are static): its device table and scratch must come from the graph's own memory
+            # pool -- nor with another capture, whose pool may be gone before this one's
+            key = key + ("captured", capture_token())
+        ent = self._tables.get(key)
+        if ent is None:
+            blob = build()
+            if not capturing and len(self._tables) >= 16:  # eager address churn: recycle the oldest eager tables
+                for k in [k for k, e in self._tables.items() if not e[5]][:8]:
+                    self._free_host.append(self._tables.pop(k)[0])
+            if not self._free_host:
+                if capturing:
+                    raise RuntimeError(f"{type(self).__name__}: out of pre-pinned table buffers under hipGraph capture")
+                self._free_host.append(self._new_host())
+            host = self._free_host.pop()
+            host.numpy()[:blob.size] = blob  # plain host memcpy into the pinned buffer
+            dev = torch.empty(host.numel(), dtype=torch.uint8, device=self.device)
+            ent = self._tables[key] = (host, dev, n, blk, torch.empty(blk, dtype=torch.float32, device=self.device), capturing,
+                                       capture_token() if capturing else None)
+            # (re)sent on every use below: under hipGraph capture the copy becomes a node reading THIS pinned buffer
+        host, dev, n, blk, partial = ent[:5]
+        dev.copy_(host, non_blocking=True)
+        return dev, n, blk, partial
+
+    def release_captured(self, token):
+        """A hipGraph captured under graph_step.capture_token() == token is gone (evicted, or its capture failed): its pinned
+        pointer table goes back to the free list (StepGraphs on_evict).  The caller guarantees the graph no longer runs."""
+        for k in [k for k, e in self._tables.items() if e[5] and e[6] == token and token is not None]:
+            self._free_host.append(self._tables.pop(k)[0])
+
+    def captured_tables(self):
+        return sum(1 for e in self._tables.values() if e[5])
+
+
+class FusedAdamW(_PinnedTables):
     def __init__(self, params, lr, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0, warmup_steps=0,
                  total_steps=0, cast_weights=False, graph_shapes=64):
         self.params = [p for p in params if p.requires_grad]
@@ -31,12 +97,10 @@ class FusedAdamW:
         self.exp_avg = [torch.zeros_like(p) for p in self.params]
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
         self.state = torch.zeros(4, dtype=torch.float32, device=self.device)  # step, lr, grad norm, clip coefficient
-        self._tables = {}  # gradient addresses -> (pinned host table, device table, n, blocks, scratch, made under capture)
         # pinned staging buffers are allocated HERE: hipHostMalloc is not allowed while a stream is capturing, and the
         # pointer table of a captured step can only be built during the capture (that is when its gradients exist)
         self.cast_weights = bool(cast_weights)
         self._cast_plan = None  # (generation, covered parameter mask, linear rows, linear blocks, tile rows, tile blocks)
-        self._table_bytes = (48 + 48 + 80) * len(self.params)  # full + linear + tile tables share one buffer
         # table rows {p, g, m, v, numel, blk0 | 0 << 32} as six u64 (csrc/optim.hip OptEntry): only column 1 (the gradient
         # address) changes between steps
         n = len(self.params)
@@ -51,11 +115,7 @@ class FusedAdamW:
         self._blocks = int(blocks.sum())
         # pinned table buffers: every captured step shape holds one for good (hipHostMalloc is not allowed under capture, so they
         # are all allocated here), eager steps rotate through up to 16 more (gradient addresses change from step to step)
-        self._free_host = [self._new_host() for _ in range(graph_shapes + 24)]
-
-    def _new_host(self):
-        t = torch.empty(self._table_bytes, dtype=torch.uint8)
-        return t.pin_memory() if self.device.type == "cuda" else t
+        self._init_tables((48 + 48 + 80) * len(self.params), graph_shapes + 24)  # full + linear + tile tables share one buffer
 
     # -- gradient pointer table: gradients are fresh tensors after every backward, so their addresses may move
     def _plan(self):
@@ -100,21 +160,16 @@ class FusedAdamW:
         return self._cast_plan
 
     def _table(self, grads, plan=None):
-        key = tuple([g.data_ptr() for g in grads])
+        ptrs = tuple([g.data_ptr() for g in grads])
+        key = ptrs
         if plan is not None:
             key = key + plan[0]  # cache generation: (invalidations, registered copies)
-        capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        if capturing:
-            # a captured step never shares a table with an eager step, even at equal gradient addresses (data-parallel bucket
-            # views are static): its device table and scratch must come from the graph's own memory pool
-            key = key + ("captured",)
-        ent = self._tables.get(key)
-        if ent is None:
+
+        def build():
             assert all(g.dtype == torch.float32 and g.is_contiguous() and g.numel() == p.numel()
                        for g, p in zip(grads, self.params)), "gradients must be dense f32 of the parameter's size"
             rows = self._rows.copy()
-            rows[:, 1] = key[:len(grads)]
-            blk = self._blocks
+            rows[:, 1] = ptrs
             blob = rows.reshape(-1).view(np.uint8)
             if plan is not None:
                 _, covered, lin, lin_blk, trow, tile_blk, tidx, _ = plan
@@ -123,34 +178,9 @@ class FusedAdamW:
                 trow = trow.copy()
                 trow["ptr"][:, 1] = rows[tidx, 1]
                 blob = np.concatenate([blob, lin.reshape(-1).view(np.uint8), trow.view(np.uint8).reshape(-1)])
-            if not capturing and len(self._tables) >= 16:  # eager address churn: recycle the oldest eager tables
-                for k in [k for k, e in self._tables.items() if not e[5]][:8]:
-                    self._free_host.append(self._tables.pop(k)[0])
-            if not self._free_host:
-                if capturing:
-                    raise RuntimeError("FusedAdamW: out of pre-pinned table buffers under hipGraph capture")
-                self._free_host.append(self._new_host())
-            host = self._free_host.pop()
-            host.numpy()[:blob.size] = blob  # plain host memcpy into the pinned buffer
-            dev = torch.empty(host.numel(), dtype=torch.uint8, device=self.device)
-            from .graph_step import capture_token
+            return blob
 
-            ent = self._tables[key] = (host, dev, len(self.params), blk,
-                                       torch.empty(blk, dtype=torch.float32, device=self.device), capturing,
-                                       capture_token() if capturing else None)
-            # (re)sent on every use below: under hipGraph capture the copy becomes a node reading THIS pinned buffer
-        host, dev, n, blk, partial = ent[:5]
-        dev.copy_(host, non_blocking=True)
-        return dev, n, blk, partial
-
-    def release_captured(self, token):
-        """A hipGraph captured under graph_step.capture_token() == token is gone (evicted, or its capture failed): its pinned
-        pointer table goes back to the free list (StepGraphs on_evict).  The caller guarantees the graph no longer runs."""
-        for k in [k for k, e in self._tables.items() if e[5] and e[6] == token and token is not None]:
-            self._free_host.append(self._tables.pop(k)[0])
-
-    def captured_tables(self):
-        return sum(1 for e in self._tables.values() if e[5])
+        return self._lookup_table(key, build, len(self.params), self._blocks)
 
     @torch.no_grad()
     def step(self):
@@ -232,6 +262,75 @@ class FusedAdamW:
             dst.copy_(src)
         for dst, src in zip(self.exp_avg_sq, sd["exp_avg_sq"]):
             dst.copy_(src)
+
+
+class GradAccumulator(_PinnedTables):
+    """Gradient accumulation over a window of micro-steps (Trainer(accumulate_grad_batches=K)) as a piece of the hot path:
+    add() is ONE multi-tensor launch (csrc/optim.hip: avsr_grad_accumulate) from this micro-step's gradients into persistent
+    buffers -- `.flat`, one f32 buffer, with a 16-byte-aligned view per parameter in `.grads`.  The window record `.window` =
+    {micro-steps so far, sum of their batch sizes} lives on the device: the first add() of a window overwrites the buffers (no
+    memset, nothing of the previous window survives), later ones add, a closing one adds and divides by the window's total batch
+    size in the same pass and empties the record.  Which of the two a micro-step is gets read on the device, so an add() captured
+    in a hipGraph is valid wherever in a window its graph is replayed; only `close` (which decides whether an optimizer step
+    follows) is the caller's.  After a closing add() the buffers hold
+
+        sum over the window's micro-steps of grads / sum of their batch_size        (`total`: / total[0] instead)
+
+    and an optimizer steps on `p.grad = .grads[i]`.  12 B per parameter and micro-step, against the optimizer's 34 to 36."""
+
+    def __init__(self, params, graph_shapes=64):
+        self.params = [p for p in params if p.requires_grad]
+        assert self.params, "no trainable parameters"
+        self.device = self.params[0].device
+        numel = np.array([p.numel() for p in self.params], dtype=np.int64)
+        padded = (numel + 3) // 4 * 4  # every view starts 16-byte aligned
+        offset = np.cumsum(padded) - padded
+        self.flat = torch.zeros(int(padded.sum()), dtype=torch.float32, device=self.device)
+        self.grads = [self.flat[o:o + n].view(p.shape) for o, n, p in zip(offset.tolist(), numel.tolist(), self.params)]
+        self.window = torch.zeros(2, dtype=torch.float32, device=self.device)  # micro-steps so far in the window, sum of B
+        blocks = (numel + _CHUNK - 1) // _CHUNK
+        n = len(self.params)
+        self._rows = np.zeros((n, 6), dtype=np.uint64)  # {p = accumulator view, g, -, -, numel, blk0}: OptEntry
+        self._rows[:, 0] = [g.data_ptr() for g in self.grads]
+        self._rows[:, 4] = numel.astype(np.uint64)
+        self._rows[:, 5] = (np.cumsum(blocks) - blocks).astype(np.uint64)
+        self._blocks = int(blocks.sum())
+        self._numel = float(numel.sum())
+        # a batch shape may be captured twice, as an open and as a closing micro-step
+        self._init_tables(48 * n, 2 * graph_shapes + 24, slab=True)
+
+    def _table(self, grads):
+        ptrs = tuple([g.data_ptr() for g in grads])
+
+        def build():
+            assert len(grads) == len(self.params) and all(
+                g.dtype == torch.float32 and g.is_contiguous() and g.numel() == p.numel() and g.device == self.device
+                for g, p in zip(grads, self.params)), "gradients must be dense f32 of the parameter's size"
+            rows = self._rows.copy()
+            rows[:, 1] = ptrs
+            return rows.reshape(-1).view(np.uint8)
+
+        return self._lookup_table(ptrs, build, len(self.params), self._blocks)
+
+    @torch.no_grad()
+    def add(self, grads, batch_size, close, total=None):
+        """One micro-step: grads (one dense f32 tensor per parameter, views at any dword offset allowed) of a micro-batch of
+        batch_size utterances.  close: this micro-step ends the window.  total: a device float that replaces the window's own
+        sum of batch sizes in the closing division (the sum over all data-parallel ranks)."""
+        grads = list(grads)
+        if any(g is None for g in grads):
+            raise RuntimeError("GradAccumulator.add(): every trainable parameter needs a gradient")
+        if total is not None:
+            assert close and total.dtype == torch.float32 and total.device == self.device and total.numel() == 1
+        table, n, blk, _ = self._table(grads)
+        ops.call("avsr_grad_accumulate", ops._ptr(table), n, blk, ops._ptr(self.window), float(batch_size), int(bool(close)),
+                 ops._ptr(total), ops._stream(table), nbytes=12.0 * self._numel)
+
+    @property
+    def position(self):
+        """(micro-steps so far in the open window, sum of their batch sizes); synchronises -- for tests and logging only"""
+        w = self.window.cpu()
+        return int(w[0]), float(w[1])
 
 
 class ShardedAdamW:

@@ -34,13 +34,16 @@ class _Hot(torch.nn.Module):
         return _forward_tensors(self.m, x, lens, y)
 
 
-def save_checkpoint(folder, epoch, model, opt, global_step, keep=10, opt_state=None):
+def save_checkpoint(folder, epoch, model, opt, global_step, keep=10, opt_state=None, micro_step=None):
     """rank 0: `epoch=N.ckpt` in the layout average_checkpoints.py / lightning.py:44 read ({"state_dict": {"model.<key>"}}),
     the `keep` newest kept (ModelCheckpoint(monitor="monitoring_step", mode="max", save_top_k=10): the monitored value
-    is the global step, so "top 10" = the ten latest), plus last.ckpt with the optimizer state."""
+    is the global step, so "top 10" = the ten latest), plus last.ckpt with the optimizer state.  global_step counts optimizer
+    steps; micro_step (when given) the batches behind them (accumulate_grad_batches > 1: the dropout counter of a resumed run)."""
     os.makedirs(folder, exist_ok=True)
     sd = {"model." + k: v.detach().cpu() for k, v in model.state_dict().items()}
     meta = {"epoch": epoch, "global_step": global_step}
+    if micro_step is not None:
+        meta["micro_step"] = micro_step
     torch.save({"state_dict": sd, **meta}, os.path.join(folder, f"epoch={epoch}.ckpt"))
     # (opt_state: the optimizer state gathered beforehand by ALL ranks -- a sharded optimizer's state_dict() is a collective)
     torch.save({"state_dict": sd, "optimizer": opt_state if opt_state is not None else opt.state_dict(), **meta},
@@ -50,8 +53,9 @@ def save_checkpoint(folder, epoch, model, opt, global_step, keep=10, opt_state=N
         os.remove(old)
 
 
-def load_checkpoint(path, model, opt):
-    """--ckpt-path resume (train.py:49 `trainer.fit(..., ckpt_path=...)`): weights, optimizer state, position."""
+def load_checkpoint(path, model, opt, meta=None):
+    """--ckpt-path resume (train.py:49 `trainer.fit(..., ckpt_path=...)`): weights, optimizer state, position.  meta: a dict that
+    receives the checkpoint's "micro_step" (None when it stores none)."""
     from . import functional as AF
 
     ck = torch.load(path, map_location="cpu")
@@ -68,6 +72,8 @@ def load_checkpoint(path, model, opt):
         warnings.warn(f"{path}: no native optimizer state; resuming with zero Adam moments at step {global_step} of the schedule")
         opt.state[0] = float(global_step)
     AF.invalidate_weight_cache()  # every cached bf16 copy belongs to the old weights
+    if meta is not None:
+        meta["micro_step"] = ck.get("micro_step")
     return int(ck.get("epoch", -1)) + 1, global_step
 
 
@@ -185,6 +191,24 @@ def fit(model, args, dev, rank=0, world=1, backend="nccl", log=print):
         AF.set_bn_sync(None)
 
 
+def _mark_last(batches, lookahead):
+    """(batch, is the last one of the iterable) -- by a look-ahead of one batch on the source; lookahead False: (batch, False)
+    straight through, nothing fetched early."""
+    if not lookahead:
+        for b in batches:
+            yield b, False
+        return
+    it = iter(batches)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    for nxt in it:
+        yield cur, False
+        cur = nxt
+    yield cur, True
+
+
 def _max_graphs():
     """hipGraphs (batch shapes) the loop keeps: 384 distinct (B, T, L) shapes at max-frames 1600 on the synthetic corpus; one
     graph holds ~50 MB of static inputs, the activations' pool is shared."""
@@ -199,6 +223,10 @@ class NativeStepper:
     feeds batches and runs callbacks, lightning.py:86-114 / train.py:30-42), so that the Trainer path runs at the speed of the
     benchmarked step instead of eager launches + torch's foreach AdamW.
 
+    args.accumulate_grad_batches = K > 1: a call is a MICRO-step -- forward + backward + one accumulate launch -- and every K-th call
+    (or one with close=True) also ends the window with the exchange and the optimizer step on the accumulated gradient
+    (_init_accumulating below; `closed_last` says which kind the last call was).
+
     stepper(x, lens, y) -> (loss, loss_ctc, loss_att, n_correct, n_tokens) as device scalars (static tensors of the graph when
     replayed: read them before the next step of the same shape).  close() removes the hooks / communicators it installed."""
 
@@ -209,6 +237,11 @@ class NativeStepper:
 
         self.model, self.args, self.dev, self.rank, self.world = model, args, dev, rank, world
         self.comms, self.buckets, self.shard = [], None, False
+        # Trainer(accumulate_grad_batches=K): K micro-batches per optimizer step (1, or the attribute absent: the step below, as ever)
+        self.accum = int(getattr(args, "accumulate_grad_batches", None) or 1)
+        if self.accum < 1:
+            raise ValueError(f"accumulate_grad_batches must be at least 1, not {self.accum}")
+        self.acc, self.micro_steps, self.closed_last, self._pos = None, 0, True, 0
         # own_stream: run every step on a stream of this object, joined to the caller's stream before and after.  A hipGraph capture
         # must never meet work bound to the legacy default stream (gradient-accumulation nodes remember the stream they were
         # created on), and a Lightning Trainer calls training_step on the default stream; fit() below already runs its whole loop
@@ -221,6 +254,9 @@ class NativeStepper:
         AF.manual_seed(42 + rank)
         self.seed_dev = seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         AF.set_seed_tensor(seed_dev)
+        if self.accum > 1:
+            self._init_accumulating(steps_per_epoch, log)
+            return
         hot = _Hot(model)
         buckets = None
         if world > 1:
@@ -331,17 +367,121 @@ class NativeStepper:
         self.stepper = StepGraphs(full_step, enabled=graph_ok, capture_after=1, thread_local=world > 1, max_graphs=_max_graphs(),
                                   on_fail=capture_failed, on_evict=released)
 
+    def _init_accumulating(self, steps_per_epoch, log):
+        """accumulate_grad_batches = K > 1.  K micro-batches on this rank count as K further ranks of the data-parallel step
+        (lightning.py:88-90: loss *= world / sum(B), then DDP's mean): the gradient handed to clip + AdamW at the end of a window is
+
+            G = (sum over ranks and micro-steps of grad loss_{r,k}) / (sum over ranks and micro-steps of B_{r,k})
+
+        An OPEN micro-step is forward + backward + one accumulate launch (optim.GradAccumulator); a CLOSING one is forward +
+        backward + accumulate-and-scale [+ the data-parallel exchange: one float, then the flat accumulator once] + the fused
+        optimizer step on the accumulator.  BatchNorm statistics and the dropout counter move per micro-step; step counter,
+        learning rate, clip, AdamW and the weight re-casts per window.  The two kinds differ in their launch lists, so each has
+        its own StepGraphs keyed by shape; where in a window an open micro-step sits is the device's business (the accumulator's
+        window record), so one open graph per shape serves every position."""
+        from . import functional as AF
+        from .graph_step import StepGraphs
+        from .optim import FusedAdamW, GradAccumulator
+
+        model, args, dev, rank, world, seed_dev = self.model, self.args, self.dev, self.rank, self.world, self.seed_dev
+        if world > 1:
+            AF.set_bn_sync(dist.group.WORLD)  # cross-rank BatchNorm as ever; no DDP wrapper, no bucket hooks
+            if os.environ.get("AVSR_DDP", "torch") != "torch" or os.environ.get("AVSR_SHARD_OPT", "0") == "1":
+                log(f"[rank {rank}] accumulate_grad_batches = {self.accum}: AVSR_DDP / AVSR_SHARD_OPT do not apply, the window's gradient "
+                    "travels as one all-reduce of the flat accumulator")
+        self.steps_per_epoch = opt_steps = -(-int(steps_per_epoch) // self.accum)  # a short last window is flushed at the epoch's end
+        opt = self.opt = FusedAdamW(model.parameters(), lr=args.lr, betas=(0.9, 0.98), weight_decay=args.weight_decay,
+                                    max_grad_norm=10.0, warmup_steps=int(args.warmup_epochs * opt_steps),
+                                    total_steps=int(args.max_epochs * opt_steps), cast_weights=dev.type == "cuda",
+                                    graph_shapes=_max_graphs())
+        params = list(model.parameters())
+        acc = self.acc = GradAccumulator(params, graph_shapes=_max_graphs())
+        warmed = set()
+
+        def capturing():
+            return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+        def micro_step(close):
+            def step(x, lens, y):
+                for p in params:  # (gradients of a replayed step live in the graph's pool: never accumulate into them)
+                    p.grad = None
+                seed_dev.add_(1)  # per micro-step: every micro-batch draws fresh dropout masks
+                AF.manual_seed(42 + rank)
+                AF.new_step()
+                AF.refresh_weight_cache()
+                loss, loss_ctc, loss_att, hits, ntok = _forward_tensors(model, x, lens, y)
+                loss.backward()
+                grads, bsz = [p.grad for p in acc.params], float(y.shape[0])
+                if close and world > 1:
+                    total = acc.window[1:2] + bsz  # this rank's window, then everybody's
+                    dist.all_reduce(total)
+                    acc.add(grads, bsz, True, total=total)
+                    dist.all_reduce(acc.flat)  # the ONE gradient-sized collective of the window
+                else:
+                    acc.add(grads, bsz, close)
+                if close:
+                    for p, g in zip(acc.params, acc.grads):
+                        p.grad = g
+                    opt.step()
+                if close not in warmed and not capturing():
+                    # once per kind, after its first eager run: the weight-copy tables are rebuilt (a host-to-device copy, illegal
+                    # under capture) by the first refresh that finds copies this step created -- or, after the first optimizer
+                    # step, copies the optimizer has just taken over -- and that must not be the refresh of a capture
+                    AF.refresh_weight_cache()
+                    warmed.add(close)
+                return loss.detach(), loss_ctc.detach(), loss_att.detach(), hits, ntok
+            return step
+
+        # hipGraph replay per batch shape and kind on one rank; the data-parallel exchange above runs on torch.distributed: eager
+        self._graph_ok = dev.type == "cuda" and not getattr(args, "no_graph", False) and world == 1
+
+        def capture_failed(e):
+            log(f"[rank {rank}] hipGraph capture failed ({type(e).__name__}: {str(e)[:160]}); eager from here on")
+            for p in params:
+                p.grad = None
+            self._graph_ok = False
+            self.open_graphs.enabled = self.close_graphs.enabled = False
+
+        def released(token):  # a graph is gone: its pinned pointer tables go back to their owners
+            opt.release_captured(token)
+            acc.release_captured(token)
+
+        # (no capture before the first optimizer step has run eagerly: it re-registers the weight copies it rewrites itself, and a
+        # graph captured earlier would go on reading the tables of before)
+        kw = dict(enabled=False, capture_after=1, max_graphs=_max_graphs(), on_fail=capture_failed, on_evict=released)
+        self.open_graphs = StepGraphs(micro_step(False), tag="open", **kw)
+        self.close_graphs = self.stepper = StepGraphs(micro_step(True), tag="close", **kw)
+        if self._graph_ok:
+            self.open_graphs.pool = self.close_graphs.pool = torch.cuda.graph_pool_handle()  # (they never run concurrently)
+
     @property
     def stats(self):
-        return self.stepper.stats
+        if self.accum == 1:
+            return self.stepper.stats
+        o, c = self.open_graphs.stats, self.close_graphs.stats
+        return dict({k: o[k] + c[k] for k in o}, open=dict(o), close=dict(c))
 
-    def __call__(self, x, lens, y):
-        if self._work is None:
+    def _step(self, x, lens, y, close):
+        if self.accum == 1:
             return self.stepper(x, lens, y)
+        self._pos += 1
+        self.closed_last = bool(close) or self._pos >= self.accum
+        out = (self.close_graphs if self.closed_last else self.open_graphs)(x, lens, y)
+        self.micro_steps += 1
+        if self.closed_last:
+            self._pos = 0
+            self.open_graphs.enabled = self.close_graphs.enabled = self._graph_ok
+        return out
+
+    def __call__(self, x, lens, y, close=None):
+        """close (accumulate_grad_batches > 1 only): None = every K-th call ends its window with an optimizer step, True = this
+        call does, whatever its position (the last batch of an epoch).  `closed_last` tells which it was."""
+        if self._work is None:
+            return self._step(x, lens, y, close)
         cur = torch.cuda.current_stream(self.dev)
         self._work.wait_stream(cur)
         with torch.cuda.stream(self._work):
-            out = self.stepper(x, lens, y)
+            out = self._step(x, lens, y, close)
         cur.wait_stream(self._work)
         return out
 
@@ -368,36 +508,53 @@ def _fit(model, args, dev, rank, world, backend, log, held):
     # number of collectives per epoch are identical on all ranks
     steps_per_epoch = source.steps_per_epoch
     ns = held["native"] = NativeStepper(model, args, dev, rank, world, steps_per_epoch, log=log, own_stream=False)
-    opt, seed_dev, stepper = ns.opt, ns.seed_dev, ns.stepper
+    opt, seed_dev, K = ns.opt, ns.seed_dev, ns.accum
+    # accumulate_grad_batches = K > 1: a call of the stepper is a MICRO-step; `global_step`, --steps, --time-last, the checkpoints
+    # and the logged lr / gnorm count optimizer steps (ceil(batches / K) per epoch: the last window of an epoch is flushed, as
+    # Lightning does), `micro_step` counts batches and drives the dropout counter and the synthetic batches' seeds
+    stepper = ns.stepper if K == 1 else ns
     held["stepper"] = stepper
     folder = os.path.join(args.exp_dir, args.exp_name) if getattr(args, "exp_dir", None) else None
-    start_epoch, global_step = 0, 0
+    start_epoch, global_step, micro_step = 0, 0, 0
     if getattr(args, "ckpt_path", None):
-        start_epoch, global_step = load_checkpoint(args.ckpt_path, model, opt)
-        seed_dev.add_(global_step)  # dropout masks are a function of (rank, global step, site): a resumed run continues them
+        meta = {}
+        start_epoch, global_step = load_checkpoint(args.ckpt_path, model, opt, meta=meta)
+        # (a checkpoint is written at the end of an epoch, where no window is open; one without the count -- written before
+        # there was accumulation, or by a Lightning Trainer -- continues from global_step * K)
+        micro_step = global_step * K if meta.get("micro_step") is None else int(meta["micro_step"])
+        seed_dev.add_(micro_step)  # dropout masks are a function of (rank, micro-step, site): a resumed run continues them
+    ns.micro_steps = micro_step
     val = source.val_batches(getattr(args, "val_batches", 0) or 0)
     max_steps = getattr(args, "steps", None)
     losses = []
     t0 = time.time()
     done = False
     mode = getattr(args, "numerics", None)  # train.py: --numerics, default "mixed" (what bench.py times); None: the caller's mode
-    tail, t_tail = int(getattr(args, "time_last", 0) or 0), None
+    tail, t_tail, micro_tail, replayed_tail = int(getattr(args, "time_last", 0) or 0), None, 0, 0
     if mode is not None:
         AF.set_mode(mode)
     for epoch in range(start_epoch, args.max_epochs):
         # reload_dataloaders_every_n_epochs=1 + shuffle=True (train.py:39, data_module.py:140): a new order every epoch
         nb = 0
-        for bi, (x, lens, y) in enumerate(source.epoch(epoch, global_step)):
+        for (x, lens, y), last in _mark_last(source.epoch(epoch, micro_step), lookahead=K > 1):
             nb += 1
-            if tail and max_steps and global_step == max_steps - tail:  # --time-last N: wall clock of the last N steps
+            if tail and max_steps and global_step == max_steps - tail and t_tail is None:  # --time-last N: wall clock of the last N steps
                 torch.cuda.synchronize() if dev.type == "cuda" else None
-                t_tail = time.perf_counter()
-            loss, loss_ctc, loss_att, hits, ntok = stepper(x, lens, y)
+                t_tail, micro_tail, replayed_tail = time.perf_counter(), micro_step, stepper.stats["replayed"]
+            if K == 1:
+                loss, loss_ctc, loss_att, hits, ntok = stepper(x, lens, y)
+            else:
+                loss, loss_ctc, loss_att, hits, ntok = stepper(x, lens, y, close=True if last else None)
+            micro_step += 1
+            if K > 1 and not ns.closed_last:
+                continue  # an open micro-step: no optimizer step yet
             global_step += 1
             if t_tail is not None and global_step == max_steps:
                 torch.cuda.synchronize() if dev.type == "cuda" else None
                 held["tail_ms"] = (time.perf_counter() - t_tail) / tail * 1e3
-                log(f"last {tail} steps: {held['tail_ms']:.2f} ms / step ({stepper.stats})")
+                per_micro = "" if K == 1 else (f", {held['tail_ms'] * tail / (micro_step - micro_tail):.2f} ms / micro-step over "
+                                               f"{micro_step - micro_tail} ({stepper.stats['replayed'] - replayed_tail} of them replays)")
+                log(f"last {tail} steps: {held['tail_ms']:.2f} ms / step{per_micro} ({stepper.stats})")
             every = getattr(args, "log_every", 10)
             if every and ((global_step - 1) % every == 0 or global_step == max_steps):
                 losses.append(float(loss.detach()))
@@ -415,7 +572,7 @@ def _fit(model, args, dev, rank, world, backend, log, held):
             log(f"epoch {epoch} validation: " + " ".join(f"{k} {v:.4f}" for k, v in metrics.items()))
         opt_state = opt.state_dict() if (folder and getattr(opt, "collective_state", False)) else None  # (every rank: a collective)
         if rank == 0 and folder:
-            save_checkpoint(folder, epoch, model, opt, global_step, opt_state=opt_state)
+            save_checkpoint(folder, epoch, model, opt, global_step, opt_state=opt_state, micro_step=micro_step)
         if world > 1:
             dist.barrier()
         if done:

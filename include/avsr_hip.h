@@ -752,6 +752,15 @@ int avsr_adamw_apply(const void* table, int n, int total_blocks, const float* su
  * data-parallel gradient exchange gathers a bucket's gradients into its flat RCCL all-reduce buffer with it (train.py:37
  * DDPStrategy: gradient averaging = scale 1 / world). */
 int avsr_multi_copy_scale(const void* table, int n, int total_blocks, float scale, avsr_stream_t stream);
+/* Gradient accumulation (Trainer(accumulate_grad_batches=K)): one micro-step of a window for n f32 tensors in ONE launch (+ a
+ * one-thread launch that moves the window record).  table entries as above with p = accumulator slice, g = this micro-step's
+ * gradient (dword-aligned views allowed; m, v unused).  window: 2 device floats {micro-steps so far in this window, sum of
+ * their batch sizes}, {0, 0} at the start of a window.  window[0] == 0: acc = g (the accumulator is overwritten, never read);
+ * else acc += g.  close != 0: also acc *= 1 / (window[1] + batch_size) -- 1 / total[0] when total != NULL (a device float: the
+ * sum over all data-parallel ranks) -- and the window returns to {0, 0}; close == 0: window += {1, batch_size}.  Whether a
+ * micro-step is the first of its window is read from the device, so a captured launch is valid at any position. */
+int avsr_grad_accumulate(const void* table, int n, int total_blocks, float* window, float batch_size, int close,
+                         const float* total, avsr_stream_t stream);
 /* The same step with the bf16 operand copies of 2-D weights (see avsr_multi_cast_transpose) rewritten in the update pass,
  * so that no separate re-cast launch re-reads the f32 weights before the next forward pass:
  *   table / n / total_blocks          every parameter (48-byte entries as above) -- gradient norm only

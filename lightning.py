@@ -144,6 +144,12 @@ class ModelModule(_Base):
         if getattr(self, "native_step", False):
             from auto_avsr_amd.train_native import NativeStepper
 
+            if int(getattr(self.args, "accumulate_grad_batches", None) or 1) > 1:
+                raise ValueError("--trainer-step native under a Lightning Trainer takes no --accumulate-grad-batches above 1: the "
+                                 "Trainer does not tell training_step which batch ends an epoch, so a short last window would not "
+                                 "be flushed.  Use --trainer-step auto (the Trainer accumulates), or the native loop (train.py "
+                                 "without pytorch_lightning, or --synthetic), which accumulates inside the replayed step")
+
             tr = self.trainer
             world = tr.num_devices * tr.num_nodes
             dev = next(self.model.parameters()).device

@@ -6,6 +6,15 @@ import os
 from argparse import ArgumentParser
 
 
+def _positive_int(text):
+    n = int(text)
+    if n < 1:
+        from argparse import ArgumentTypeError
+
+        raise ArgumentTypeError(f"must be at least 1, not {n}")
+    return n
+
+
 def parse_args(argv=None):
     p = ArgumentParser()
     p.add_argument("--exp-dir", default="./exp", type=str, help="directory for checkpoints and logs")
@@ -54,6 +63,10 @@ def parse_args(argv=None):
     p.add_argument("--grad-wire", default=None, choices=["f32", "bf16"],
                    help="format of the gradient buckets on the xGMI links (AVSR_DDP=buckets): f32 = the reference's DDP all-reduce "
                         "(default), bf16 = half the bytes per link, bf16 sums across the ranks")
+    p.add_argument("--accumulate-grad-batches", default=1, type=_positive_int,
+                   help="micro-batches per optimizer step (Lightning's Trainer argument): their gradients are summed on the device "
+                        "and divided by the window's total batch size; --steps, --time-last, checkpoints, the schedule and the "
+                        "logged lr / gnorm count optimizer steps.  1: one optimizer step per batch")
     p.add_argument("--log-every", default=10, type=int)
     p.add_argument("--time-last", default=0, type=int, help="report the wall clock per step of the last N of --steps steps")
     return p.parse_args(argv)
@@ -72,6 +85,8 @@ def get_trainer(args):
                    strategy=DDPStrategy(find_unused_parameters=False),
                    callbacks=[ckpt, LearningRateMonitor(logging_interval="step")],
                    reload_dataloaders_every_n_epochs=1,
+                   # (--trainer-step native refuses N > 1 when the fit starts, lightning.ModelModule.on_fit_start)
+                   accumulate_grad_batches=int(getattr(args, "accumulate_grad_batches", 1) or 1),
                    # (manual optimisation: Lightning refuses gradient_clip_val; the fused step clips at 10 itself)
                    gradient_clip_val=None if getattr(args, "trainer_step", "auto") == "native" else 10.0)
 
